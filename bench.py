@@ -30,10 +30,21 @@ than N GPUs fails instead of reporting fewer.
 Each loop runs untimed passes for SETTLE_S of wall time before its W warmup steps (the GPU's clock
 ramp out of idle: a 100-step config-3 loop is ~20 ms), then times exactly K steps.
 
+A plain run (``--gpus N --steps K --warmup W``) does only what the headline needs: it sets up the
+genome, warms up, times the K steps, writes the outputs (``--dump-outputs DIR``) and prints the line.
+Everything else -- the kernels alone on one stream, the dense kernel samples, the single-stream pass, the
+run without Fst, 20 kb + 500 kb from one pass, ``config2_weak``, ``config4_sims``,
+``config5_snp_windows``, ``cpu_baseline`` and ``end_to_end_vcf_csv`` -- runs only with ``--full`` (the
+``--no-*`` options then drop single legs); without it those keys are absent or null.
+
+``--dump-outputs DIR``: after the timed steps, what the headline's last timed step computed -- the window
+table a caller receives, one ``DIR/<field>.npy`` (float64) per field of the 64-B records plus ``fst.npy``
+(dump_outputs).  The genome is seeded, so two builds run with the same arguments write comparable files.
+
 Prints ONE JSON line on rank 0.  ``roofline``: the dominant kernel (k_scan_w) of the headline workload,
 algorithmic bytes per launch over its average duration in the timed steps (HIP start / end events in
-its dispatch packets, >= 10 of the timed passes, on the stream it runs on; its one-stream duration is
-rank0.scan_alone_ms).  ``cpu_baseline``: the C oracle (the reference's dense per-window algorithm,
+its dispatch packets, 2 timed passes per plan, on the stream it runs on; with ``--full`` its one-stream
+duration is rank0.scan_alone_ms).  ``cpu_baseline``: the C oracle (the reference's dense per-window algorithm,
 OpenMP) on the box's host cores over a bounded sample of the same genome (its first chromosome).
 """
 from __future__ import annotations
@@ -187,6 +198,39 @@ def end_to_end(n_rec=1_000_000, nchrom=8, seed=3):
             "workload": f"synthetic BGZF VCF, {n_rec} records x 32 samples (18 uv + 14 bv), {nchrom} chromosomes; "
                         "python -m sfs2d --window 20000 --window 500000 --snp-window 500 (the reference "
                         "script's three scans) from the file on disk to the three CSVs written, second run"}
+
+
+DUMP_MAX_BYTES = 60_000_000   # all files of one dump together (under 64 MB with their headers)
+
+
+def dump_outputs(outdir, table, fst):
+    """``--dump-outputs``: the window table of the last timed step as a caller of the scan receives it,
+    one float64 file per field of the 64-B records (uint32 fields are exact in float64) and ``fst.npy``
+    (one value per slot, all ranks' slots at N > 1).  T2D / T1D / Fst may hold NaN or +-inf (no
+    qualifying SNP, zero background): ``<name>.npy`` holds 0.0 there and ``<name>_class.npy`` says which
+    (0 finite, 1 NaN, 2 +inf, 3 -inf), so that files compare with a plain tolerance.  A dump over
+    DUMP_MAX_BYTES keeps a fixed, seeded sample of the rows (the same rows in every file)."""
+    from sfs2d import _lib as L
+    recs = np.frombuffer(np.ascontiguousarray(table).tobytes(), dtype=L.WINDOW_DTYPE)
+    arrays = {name: recs[name].astype(np.float64) for name in L.WINDOW_DTYPE.names}
+    if fst is not None:
+        arrays["fst"] = np.asarray(fst, np.float64)[: len(recs)]
+    floats = [n for n in ("t2d", "t1d_p1", "t1d_p2", "fst") if n in arrays]
+    for name in floats:
+        a = arrays[name]
+        cls = np.where(np.isnan(a), 1.0, np.where(a == np.inf, 2.0, np.where(a == -np.inf, 3.0, 0.0)))
+        arrays[name] = np.where(cls == 0.0, a, 0.0)
+        arrays[name + "_class"] = cls
+    rows = len(recs)
+    keep = DUMP_MAX_BYTES // (8 * (len(arrays) + 1))   # + row.npy
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["row"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, np.float64))
+    return {"dir": outdir, "files": len(arrays), "rows": int(min(rows, keep)), "of_rows": rows}
 
 
 SHARED_GPU = os.environ.get("SFS2D_BENCH_SHARED_GPU") == "1"
@@ -521,7 +565,9 @@ def run_loop_gathered(cx, plans, steps, warmup, label, nstreams=2, time_kernels=
             q.set_fst_out(None)
     mine = bufs[(g - 1) % NB][:rec_b].view(rows, 64)[:nrec].cpu().numpy()
     allr = gathered[(g - 1) % NB].view(cx.world, per)[:, :rec_b].reshape(-1, 64).cpu().numpy()
-    return {"dt": dt, "device_ms": span_ms, "gather_ms": gat_ms, "t_enq": t_enq, "rows": rows,
+    allf = (gathered[(g - 1) % NB].view(cx.world, per)[:, P * rec_b: P * rec_b + fst_b].reshape(-1).cpu().numpy()
+            .view(np.float64) if fst else None)
+    return {"fst_gathered": allf, "dt": dt, "device_ms": span_ms, "gather_ms": gat_ms, "t_enq": t_enq, "rows": rows,
             "gathered": allr, "mine": mine, "streams": nstreams, "settle_passes": settle,
             "k_timed_ms": k_timed, "k_timed_samples": nk, "windows_per_pass_gathered": nwin_pass,
             "gathers": g - g0, "group": P, "gathered_bytes_per_pass": cx.world * (rec_b + fst_b)}
@@ -618,18 +664,23 @@ def config3_strong(cx, args):
         plans = [cx.eng.plan(dev, cfg) for _ in range(ns)]
         r = run_loop(cx, plans, args.steps, args.warmup, "config 3", time_kernels=True)
         total_windows = n_windows(r["gathered"])
+        if args.dump_outputs:   # the last timed step's Fst column, from the plan that ran it
+            r["fst_gathered"] = plans[(args.steps - 1) % ns].read_fst()
     win_rank = n_windows(r["mine"])
-    k1, _, k3 = kernel_times(plans[0])
-    dense = dense_kernel_samples(cx, plans, 10, args.steps) if cx.rank == 0 else None
+    extra = {}
+    if args.dump_outputs and cx.rank == 0:
+        extra["dumped"] = dump_outputs(args.dump_outputs, r["gathered"], r["fst_gathered"])
+    k1 = k3 = dense = one = None
+    if args.full:
+        k1, _, k3 = kernel_times(plans[0])
+        dense = dense_kernel_samples(cx, plans, 10, args.steps) if cx.rank == 0 else None
     # a single scan of the genome as a user runs it: the default plan (no scan grid cap), back to back
     # on one stream
-    one = None
-    if cx.rank == 0:
+    if args.full and cx.rank == 0:
         solo = cx.eng.plan(dev, ScanConfig(n1p=POP, n2p=POP, window=WS, fst=True))
         one = single_pass_ms(cx, solo, runs=50)
         solo.close()
-    extra = {}
-    if cx.world == 1 and not args.no_variants:
+    if args.full and cx.world == 1 and not args.no_variants:
         # what Hudson's Fst costs the pass: the same loop without Fst (the reference's statistics) and
         # with it, interleaved three times each (box-to-box clock drift moves both alike); medians
         cfg2 = ScanConfig(n1p=POP, n2p=POP, window=WS, fst=False, scan_wgs_per_cu=1)
@@ -887,6 +938,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: kernels alone, dense samples, single-stream pass, "
+                         "the run without Fst, 20 kb + 500 kb, configs 2 / 4 / 5, the CPU baseline, VCF -> CSV end to end")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the window table of the last timed step as DIR/<field>.npy (float64) and DIR/fst.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the VCF -> CSV end-to-end timing")
     ap.add_argument("--no-config2", action="store_true", help="skip the config-2 (weak scaling) key")
@@ -942,9 +998,9 @@ def main():
     cx = Ctx(world, rank, local, max(2, args.streams))
 
     c3, genome = config3_strong(cx, args)
-    c2 = None if args.no_config2 else config2_weak(cx, args)
+    c2 = config2_weak(cx, args) if args.full and not args.no_config2 else None
     c4 = c5 = None
-    if world == 1 and not args.no_sims:
+    if args.full and world == 1 and not args.no_sims:
         c5 = config5_snpwin(cx, args)
         c4 = config4_sims(cx, args)
 
@@ -957,7 +1013,7 @@ def main():
         traffic, tsrc = pmc_traffic(r0["scan_kernel"], r0["scan_grid_threads"])
         line = {
             "metric": METRIC, "value": c3["value"], "unit": "windows/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": c3["ms_per_step"], "higher_is_better": True, "scaling": "strong",
+            "warmup": args.warmup, "full": args.full, "ms_per_step": c3["ms_per_step"], "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic (SURVEY 8d generator, seed 777)",
             "config": {"workload": "configs[2]: synthetic whole genome, 32 chromosomes x 1.5625e6 = 5e7 SNPs, 20 kb "
                                    "windows, n1=n2=50 haploid (pop_size 25/25), per-chromosome background, "
@@ -1004,9 +1060,11 @@ def main():
             line["config4_sims"] = c4
         if c5 is not None:
             line["config5_snp_windows"] = c5
-        if not args.no_cpu_baseline and world == 1:
+        if "dumped" in c3:
+            line["dumped"] = c3["dumped"]
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(genome.subset_chroms([0]))
-        if not args.no_e2e and world == 1:
+        if args.full and not args.no_e2e and world == 1:
             line["end_to_end_vcf_csv"] = end_to_end()
         if SHARED_GPU and world > 1:
             line["shared_gpu_rehearsal"] = "SFS2D_BENCH_SHARED_GPU: every rank on GPU 0 over gloo -- a code-path check, not a measurement"

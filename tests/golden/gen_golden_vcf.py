@@ -14,8 +14,8 @@ and a second popmap with three populations are the population maps.
 Expected outputs come from the REFERENCE's own ``make_data_dict_vcf`` run unmodified (loaded as in
 gen_golden.py); only data is written: the test VCF in two encodings (BGZF, one-member gzip;
 the tests decompress it for the plain-text case), the popmaps, and ``vcf_expected_<popmap>.npz`` with the dict flattened to arrays.
-A digest of the full ECB_LDprunedv2.vcf.gz result is stored too (checked only where the
-reference data exists).
+A digest of the full ECB_LDprunedv2.vcf.gz result is stored too, with the file's text as
+``ECB_LDprunedv2.vcf.xz``.
 
 Run:  python tests/golden/gen_golden_vcf.py
 """
@@ -158,6 +158,10 @@ def main():
     manifest["full_ECB_LDprunedv2"] = {"records": len(full), "digest": digest(full),
                                        "note": "reference vcf_pruned/ECB_LDprunedv2.vcf.gz + popmap.txt"}
     print("full", len(full))
+    # the whole data file as a fixture (its text, xz: under the size limit for a committed file)
+    import lzma
+    with gzip.open(src, "rb") as fh, open(os.path.join(HERE, "ECB_LDprunedv2.vcf.xz"), "wb") as out:
+        out.write(lzma.compress(fh.read(), preset=9))
     with open(os.path.join(HERE, "vcf_manifest.json"), "w") as fh:
         json.dump(manifest, fh, indent=1)
 

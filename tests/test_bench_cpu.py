@@ -38,6 +38,37 @@ def test_config3_cuts(world):
         assert sizes.min() == sizes.max() == p.n // world
 
 
+def test_dump_outputs(tmp_path, monkeypatch):
+    # --dump-outputs: one float64 file per record field + fst; NaN / inf moved into <name>_class.npy
+    p = _genome()
+    ocfg = O.Cfg(25, 25)
+    bgs = O.chrom_backgrounds(p, ocfg)
+    recs = FR.bp_records(p, 20000, ocfg, lambda c: bgs[c])
+    fst = np.linspace(-0.1, 0.9, len(recs))
+    fst[[0, 3, 5]] = [np.nan, np.inf, -np.inf]
+    info = bench.dump_outputs(str(tmp_path / "a"), recs.view(np.uint8).reshape(-1, 64), fst)
+    assert info["rows"] == info["of_rows"] == len(recs)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == set(L.WINDOW_DTYPE.names) | {"fst"} | {n + "_class" for n in ("t2d", "t1d_p1", "t1d_p2", "fst")}
+    assert all(a.dtype == np.float64 and a.shape == (len(recs),) and np.isfinite(a).all() for a in got.values())
+    for name in ("chrom", "begin", "end", "snp_count", "n2", "flags"):
+        assert np.array_equal(got[name], recs[name].astype(np.float64))
+    assert got["fst_class"][:6].tolist() == [1, 0, 0, 2, 0, 3] and got["fst"][[0, 3, 5]].tolist() == [0, 0, 0]
+    ok = got["fst_class"] == 0
+    assert np.array_equal(got["fst"][ok], fst[ok])
+    ok = np.isfinite(recs["t2d"])
+    assert np.array_equal(got["t2d_class"] == 0, ok) and np.array_equal(got["t2d"][ok], recs["t2d"][ok])
+    # over the size limit: the same seeded rows in every file, run after run
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 19 * 50)
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), recs.view(np.uint8).reshape(-1, 64), fst)
+        assert info["rows"] == 50 < info["of_rows"]
+    rows = np.load(tmp_path / "b" / "row.npy").astype(np.int64)
+    assert len(rows) == 50 and np.array_equal(rows, np.load(tmp_path / "c" / "row.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "wid.npy"), recs["wid"][rows].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "b" / "fst_class.npy"), got["fst_class"][rows])
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

@@ -260,11 +260,15 @@ def test_missing_files(tmp_path):
         V.read_vcf(str(tmp_path / "nope.vcf.gz"), os.path.join(GOLD, "popmap_ref.txt"))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/vcf_pruned/ECB_LDprunedv2.vcf.gz"),
-                    reason="reference data not present")
-def test_full_reference_vcf_digest():
+def test_full_reference_vcf_digest(tmp_path):
+    # the reference's whole data file (tests/golden/ECB_LDprunedv2.vcf.xz: its text, xz for the size of
+    # the fixture), written back as the plain gzip the reference ships; popmap_ref.txt is its popmap.txt
+    import lzma
     sys.path.insert(0, GOLD)
     from gen_golden_vcf import digest
     man = json.load(open(os.path.join(GOLD, "vcf_manifest.json")))["full_ECB_LDprunedv2"]
-    d = V.make_data_dict_vcf("/root/reference/vcf_pruned/ECB_LDprunedv2.vcf.gz", "/root/reference/popmap.txt")
+    path = str(tmp_path / "ECB_LDprunedv2.vcf.gz")
+    with lzma.open(os.path.join(GOLD, "ECB_LDprunedv2.vcf.xz"), "rb") as fh:
+        open(path, "wb").write(gzip.compress(fh.read(), 1))
+    d = V.make_data_dict_vcf(path, os.path.join(GOLD, "popmap_ref.txt"))
     assert len(d) == man["records"] and digest(d) == man["digest"]

@@ -2,7 +2,7 @@
 # One GPU call, as a list of steps, each under its own time limit; the first failing step ends the call.
 # usage: bash tools/gpu.sh <tag> <step>...      outputs under gpurun_out/<tag>/
 #   tests[=<pytest -k expr>]  the -m gpu suite       smoke    __graft_entry__.smoke()
-#   bench                     python bench.py         driver   the driver's bench command (20 steps)
+#   bench                     python bench.py --full  driver   the driver's bench command (20 steps, headline only)
 #   rocprof                   rocprofv3 kernel trace + stats of the bench
 #   pmc                       HBM bytes of the bench and config 3 (tools/pmc_bench.sh)
 #   sq3                       SQ / byte counter passes over config 3 with Fst (tools/pmc_k3.sh)
@@ -23,13 +23,13 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
       tail -1 $OUT/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1 || { tail -30 $OUT/bench.log; exit 1; }
+      timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1 || { tail -30 $OUT/bench.log; exit 1; }
       tail -1 $OUT/bench.log | cut -c1-600 ;;
     driver)
       timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1 || { tail -30 $OUT/bench_driver.log; exit 1; }
       tail -1 $OUT/bench_driver.log | cut -c1-600 ;;
     rocprof)
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --no-cpu-baseline --no-e2e \
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --full --no-cpu-baseline --no-e2e \
         > $OUT/rocprof_bench.log 2>&1 || { tail -20 $OUT/rocprof_bench.log; exit 1; }
       find $OUT/prof -name "*stats*" ;;
     pmc) bash tools/pmc_bench.sh $TAG || exit 1 ;;
