@@ -207,6 +207,7 @@ struct sfs2d_plan {
   bool fst_win = false;           // Fst by window kernels (fst_windows) instead of k_prep's sums
   bool fst_scan = false;          // Fst summed by k_scan_w itself (counts plans, small grids): k_prep has no Fst work
   bool fst_mask = true;           // Fst in the scan: the data set has SNPs with < 2 called alleles (k_scan_w FST 3 / 5)
+  bool gate = false;              // Fst in the scan, folded, called counts within (n1, n2): k_scan_w's GATE variants
   int nfst = 0;                   // k_bg_slice's extra Fst workgroups
 };
 
@@ -266,9 +267,9 @@ int repl_par(const sfs2d_plan* pl) { return pl->fused ? plan_par(pl) : 0; }
 // what the scan kernels stream per SNP: the bins k_prep wrote, or (counts plans) the counts themselves
 const uint32_t* scan_src(const sfs2d_plan* pl) { return pl->cnt ? pl->data->counts : pl->d_bins; }
 
-template <bool P16, bool FUSED, int FST, bool CNT>
+template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false>
 void launch_scan_w(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
-  hipExtLaunchKernelGGL((k_scan_w<P16, FUSED, FST, CNT>), dim3((unsigned)pl->chunks.size()), dim3(SBLOCK), pl->scan_lds,
+  hipExtLaunchKernelGGL((k_scan_w<P16, FUSED, FST, CNT, GATE>), dim3((unsigned)pl->chunks.size()), dim3(SBLOCK), pl->scan_lds,
                      CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_lp, pl->d_head,
                      per_chrom, pl->ctx->d_lnx, pl->ctx->d_df, out, pl->d_err, bp, pl->d_repl, pl->d_bcount,
                      plan_par(pl), pl->d_leaves, pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels,
@@ -308,7 +309,15 @@ hipError_t launch_scan_c(sfs2d_plan* pl, sfs2d_window* out) {
   } else if (pl->G == WAVE) {
     if constexpr (CNT) {
       if (pl->fst_scan) {
-        if (pl->fst_mask) {
+        if (pl->gate) {   // (no SNP's key can leave the inner grid: the variants without the range test)
+          if (pl->fst_mask) {
+            if (pl->fused) launch_scan_w<P16, true, 3, CNT, true>(pl, out, per_chrom, bp);
+            else launch_scan_w<P16, false, 3, CNT, true>(pl, out, per_chrom, bp);
+          } else {
+            if (pl->fused) launch_scan_w<P16, true, 2, CNT, true>(pl, out, per_chrom, bp);
+            else launch_scan_w<P16, false, 2, CNT, true>(pl, out, per_chrom, bp);
+          }
+        } else if (pl->fst_mask) {
           if (pl->fused) launch_scan_w<P16, true, 3, CNT>(pl, out, per_chrom, bp);
           else launch_scan_w<P16, false, 3, CNT>(pl, out, per_chrom, bp);
         } else {
@@ -811,6 +820,9 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   if (rc) return rc;
   sfs2d_plan* pl = new sfs2d_plan();
   pl->ctx = ctx; pl->data = data; pl->prm = *prm; pl->K = K;
+  // no SNP of the data set has more called alleles than 2 pop_size in either population (max_nc1 / max_nc2)
+  const bool nc_ok = data->max_nc1 <= (uint32_t)K.n1 && data->max_nc2 <= (uint32_t)K.n2;
+  pl->K.nc_ok = nc_ok ? 1 : 0;
   const bool bp = prm->window_mode == SFS2D_WINDOW_BP;
   pl->do_seg = bp;
   pl->do_bg = prm->bg_mode == SFS2D_BG_PER_CHROM;
@@ -1041,6 +1053,11 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
       if (hipFuncGetAttributes(&fa, f) != hipSuccess || pl->scan_lds + fa.sharedSizeBytes > 160 * 1024) pl->fst_scan = false;
     }
   }
+  // folded, and every called count within 2 pop_size (the condition of k_scan_gw's triangle below): a
+  // folded key has x1 <= n1, x2 <= n2 and x1 + x2 <= (n1 + n2) / 2 -- inside the grid and never the excluded
+  // last bin -- so the scan's per-SNP range test on it is dead (k_scan_w's GATE variants, built for Fst in
+  // the scan).  Over-called or unfolded data keep the test.
+  pl->gate = pl->fst_scan && prm->fold && nc_ok;
   const PwTree pw = pw_plan(K.nb2 - 3);
   pl->fst_mask = data->low_nc;
   pl->fst_win = pl->sliced && bp && pl->fst && !pl->fst_scan;
@@ -1060,6 +1077,10 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
                           (const void*)k_scan_w<true, false, 2, true>, (const void*)k_scan_w<false, false, 2, true>,
                           (const void*)k_scan_w<true, true, 3, true>, (const void*)k_scan_w<false, true, 3, true>,
                           (const void*)k_scan_w<true, false, 3, true>, (const void*)k_scan_w<false, false, 3, true>,
+                          (const void*)k_scan_w<true, true, 2, true, true>, (const void*)k_scan_w<false, true, 2, true, true>,
+                          (const void*)k_scan_w<true, false, 2, true, true>, (const void*)k_scan_w<false, false, 2, true, true>,
+                          (const void*)k_scan_w<true, true, 3, true, true>, (const void*)k_scan_w<false, true, 3, true, true>,
+                          (const void*)k_scan_w<true, false, 3, true, true>, (const void*)k_scan_w<false, false, 3, true, true>,
                           (const void*)k_scan_g<true, false, false>, (const void*)k_scan_g<false, false, false>,
                           (const void*)k_scan_g<true, true, false>, (const void*)k_scan_g<false, true, false>,
                           (const void*)k_scan_g<true, false, true>, (const void*)k_scan_g<false, false, true>,
@@ -1087,6 +1108,12 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     else if (pl->gw)
       oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<true, true, true>, WAVE, pl->scan_lds)
                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<false, true, true>, WAVE, pl->scan_lds);
+    else if (pl->gate && pl->fused)
+      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, true, 2, true, true>, SBLOCK, pl->scan_lds)
+                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, true, 2, true, true>, SBLOCK, pl->scan_lds);
+    else if (pl->gate)
+      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, false, 2, true, true>, SBLOCK, pl->scan_lds)
+                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, false, 2, true, true>, SBLOCK, pl->scan_lds);
     else if (pl->fst_scan && pl->fused)
       oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, true, 2, true>, SBLOCK, pl->scan_lds)
                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, true, 2, true>, SBLOCK, pl->scan_lds);

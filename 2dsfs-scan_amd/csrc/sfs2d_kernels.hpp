@@ -143,6 +143,8 @@ struct KParams {
                          // x1 + x2 <= n, (n+1)(n+2)/2 of them, stored as a triangle (0: full grid)
   int jnt;               // k_prep (counts plans, LDS histogram): the joint (alt1, alt2) histogram, see prep_tile
   int lnl;               // k_scan_gw: ln(x) for x < LNL in the wave's LDS (when it costs no occupancy)
+  int nc_ok;             // the data's called counts r + a stay within (n1, n2) in every SNP (known at upload:
+                         // max_nc1 <= n1 and max_nc2 <= n2): k_prep's fast steps skip the per-step test for it
 };
 constexpr int LNL = 512;   // k_scan_gw's LDS ln table (window totals and 1D bin counts below it)
 
@@ -491,19 +493,23 @@ __device__ __forceinline__ void cls_fields(const KParams& P, uint32_t c, uint32_
   g2 = gv >> 16;
 }
 
-// k_scan_w's per-SNP classification: cls_fields' k2, and both folded 1D bins packed (u16 pairs, times BS)
+// k_scan_w's per-SNP classification: cls_fields' k2, and both folded 1D bins packed (a u16 pair)
 // with no range test -- the excluded bins 0 (fixed in the population) and n_p (MAF 1/2) are counted like the
 // others and dropped at the window's end; counts above 2 pop_size (an error k_prep reports) clamp to n_p
-template <uint32_t BS>   // gp in bytes: the bins times BS (the LDS bytes per 1D bin)
+// GATE (folded plans of data whose called counts stay within 2 pop_size in both populations: the
+// upload-time max_nc1 <= n1 and max_nc2 <= n2): the folded key has x1 <= n1, x2 <= n2 and x1 + x2 <=
+// (n1 + n2) / 2, so it can neither leave the grid nor be the excluded last bin (n1, n2) -- no range test;
+// and a <= n makes min(a, n - a) <= n_p, so the 1D bins need no clamp either
+template <bool GATE = false>
 __device__ __forceinline__ void cls_k2g(const KParams& P, uint32_t c, uint32_t& k2, uint32_t& gp) {
   const bool sw = (int)__builtin_amdgcn_udot4(c, 0x01000100u, 0u, false) > P.fold_thr;
   const uint32_t x = sw ? c : (c >> 8);
   const uint32_t kk = __builtin_amdgcn_udot4(x, P.kmul, 0u, false);
-  k2 = kk < (uint32_t)P.nb2 - 1u ? kk : 0u;
+  k2 = GATE ? kk : (kk < (uint32_t)P.nb2 - 1u ? kk : 0u);
   const u16x2 a = as_u16x2(__builtin_amdgcn_perm(0u, c, 0x0c030c01u));      // (a1, a2)
   const u16x2 g = __builtin_elementwise_min(a, as_u16x2(P.n12) - a);         // min(a, n - a)
   const u16x2 np = {(unsigned short)P.n1p, (unsigned short)P.n2p};
-  gp = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(g, np) * (u16x2){(unsigned short)BS, (unsigned short)BS});
+  gp = __builtin_bit_cast(uint32_t, GATE ? g : __builtin_elementwise_min(g, np));
 }
 
 // the per-SNP source of the scan kernels: the bins k_prep wrote, or (CNT) the counts, classified
@@ -963,15 +969,22 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
     // (called allele counts r + a by byte dot products)
     auto nc1 = [](uint32_t c) { return __builtin_amdgcn_udot4(c, 0x00000101u, 0u, false); };
     auto nc2 = [](uint32_t c) { return __builtin_amdgcn_udot4(c, 0x01010000u, 0u, false); };
-    const bool bad = (int)(max(max(nc1(ca.x), nc1(ca.y)), max(nc1(ca.z), nc1(ca.w))) > (uint32_t)P.n1) |
-                     (int)(max(max(nc2(ca.x), nc2(ca.y)), max(nc2(ca.z), nc2(ca.w))) > (uint32_t)P.n2);
+    // (P.nc_ok: the upload found no such SNP in the data set; the test -- 8 dot products, 6 max, 2 compares
+    // and a ballot per step -- then runs nowhere)
+    auto any_bad = [&]() -> bool {
+      const bool bad = (int)(max(max(nc1(ca.x), nc1(ca.y)), max(nc1(ca.z), nc1(ca.w))) > (uint32_t)P.n1) |
+                       (int)(max(max(nc2(ca.x), nc2(ca.y)), max(nc2(ca.z), nc2(ca.w))) > (uint32_t)P.n2);
+      return __ballot(bad) != 0ull;
+    };
     // the masked edge path: a step reaching outside the tile (only a chromosome's first / last tile
     // has unaligned ends: the host puts tile edges on multiples of 4 SNPs) or holding the
     // chromosome's first or last SNP (window starts / ends there whatever the neighbours' ids)
     const bool edge = base < t.begin || base + STEP > t.end || base <= t.cb || base + STEP >= t.ce;   // block-uniform
     using T_ = std::true_type;
     using F_ = std::false_type;
-    if (!FASTOK || edge || __ballot(bad)) process(T_{}, F_{}, ia, ca, pa, aav, wpa, wna);   // exact, masked
+    bool exact = !FASTOK || edge;   // block-uniform; then wave-uniform
+    if (!exact && !P.nc_ok) exact = any_bad();
+    if (exact) process(T_{}, F_{}, ia, ca, pa, aav, wpa, wna);   // exact, masked
     else {
 #ifdef SFS2D_MARK
       asm volatile("; HOT_BEGIN");
@@ -2473,12 +2486,14 @@ __device__ __forceinline__ void lds_copy_d(double* dst, const double* __restrict
 // membership = an inner 2D bin; the unfolded last bin in the rare pass), fp64 lane sums in a fixed order
 // and two wave sums per window: k_prep then runs without the Fst work (DESIGN.md "Fst placement");
 // 3: as 2, for data sets where some SNP has < 2 called alleles in a population (those SNPs masked out)
-template <bool P16, bool FUSED, int FST, bool CNT>
+// GATE: cls_k2g's (the per-SNP key needs no range test; the host selects it from the data's largest counts)
+template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false>
 // (wgi: the work item -- chunks[wgi] -- and nwg the items of the launch: k_scan_w's block index and grid)
 __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_t nwg, SCAN_W_ARGS) {
   constexpr bool FSTIN = FST >= 2;
   constexpr bool FMASK = FST == 3;
   static_assert(!FSTIN || CNT, "Fst in the scan reads the counts");
+  static_assert(!GATE || CNT, "the gate is a property of the counts the scan classifies");
   constexpr int DT = LNT;   // D(r) entries in LDS
   constexpr int R1U = R1;
   constexpr int NWV = SBLOCK / WAVE;
@@ -2875,8 +2890,11 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
             r1 = *(const lds_d2*)(uintptr_t)(rtb + 16u * n1c);
             r2 = *(const lds_d2*)(uintptr_t)(rtb + 16u * n2c);
           }
-          fq[2 * q] = make_double2((double)a1 * r1.x, (double)__umul24(a1, a1 - 1u) * r1.y);
-          fq[2 * q + 1] = make_double2((double)a2 * r2.x, (double)__umul24(a2, a2 - 1u) * r2.y);
+          // a (a - 1) as one fp64 fma on the converted a (exact: a <= 255; a = 0 gives +0, FMASK's value) --
+          // the integer form was an add, a 24-bit multiply and a second conversion per population
+          const double d1 = (double)a1, d2 = (double)a2;
+          fq[2 * q] = make_double2(d1 * r1.x, fma(d1, d1, -d1) * r1.y);
+          fq[2 * q + 1] = make_double2(d2 * r2.x, fma(d2, d2, -d2) * r2.y);
         }
       }
     };
@@ -2890,8 +2908,8 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       for (int q = 0; q < 2; ++q) {
         const uint32_t w = ww[q];
         uint32_t k2, gp;   // gp: the folded 1D bins of both populations (u16 pair; excluded ones included)
-        if (CNT) cls_k2g<4 * R1>(P, w, k2, gp);
-        else { k2 = bin_k2(w); gp = (bin_g1(w) | (bin_g2(w) << 16)) * (4u * R1); }
+        if (CNT) cls_k2g<GATE>(P, w, k2, gp);
+        else { k2 = bin_k2(w); gp = bin_g1(w) | (bin_g2(w) << 16); }
         in2[q] = k2 != 0u;   // (one compare: the ballot, the atomic's exec mask, the rank's select)
         n2 += __popcll(__ballot(in2[q]));
         // low five bits: (k2 & 1) << 4, the u16 half's shift
@@ -2914,7 +2932,13 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
         // window's end drops bins 0 and n_p and counts n1a / n1b from them)
         // (bin 0 -- the fixed SNPs and every padding slot -- counted by ballot with its atomics on lane-private
         // words measured slower: profiles/r06p_scan_bin0_ballot_ab.txt)
-        const uint32_t u1 = a1b + (gp & 0xffffu), u2 = a2b + (gp >> 16);
+        // (the bin's address base + bin * BS1 as one 16-bit multiply-add per population, the second on gp's
+        // upper half: scaling the pair, masking and adding took four operations)
+        constexpr int BS1 = 4 * R1;   // LDS bytes per 1D bin (an inline constant)
+        static_assert(BS1 <= 64, "the multiplier must be an inline constant");
+        uint32_t u1, u2;
+        asm("v_mad_u32_u16 %0, %1, %3, %2" : "=v"(u1) : "v"(gp), "v"(a1b), "n"(BS1));
+        asm("v_mad_u32_u16 %0, %1, %3, %2 op_sel:[1,0,0,0]" : "=v"(u2) : "v"(gp), "v"(a2b), "n"(BS1));
         if (!(SFS2D_ABL & 2)) {
           __hip_atomic_fetch_add((lds_u32*)(uintptr_t)u1, one1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           __hip_atomic_fetch_add((lds_u32*)(uintptr_t)u2, one1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2946,9 +2970,11 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       double d[2], lp[2];
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        // D[LNT-1] = 0: ranks past the table add 0 (clampd windows); elsewhere rank < nsnp <= LNT-1 and
-        // the min is a no-op, cheaper than selecting it per window
-        d[q] = (SFS2D_ABL & 4) ? (double)rk[q] : Dt[min(rk[q], (uint32_t)LNT - 1u)];
+        // D[LNT-1] = 0: ranks past the table add 0 (clampd windows).  The first 8 rows (keep) need no
+        // clamp: a rank is the number of SNPs counted in the bin before this one, at most 8 * 64 - 1 =
+        // LNT-1 there; only the streamed rows can pass the table
+        static_assert(8 * WAVE <= LNT, "a rank of the first 8 rows must stay inside the D table");
+        d[q] = (SFS2D_ABL & 4) ? (double)rk[q] : Dt[keep ? rk[q] : min(rk[q], (uint32_t)LNT - 1u)];
         lp[q] = (SFS2D_ABL & 4) ? (double)kk[q] : LPl[kk[q]];
       }
       const double t = (d[0] - lp[0]) + (d[1] - lp[1]);
@@ -3134,10 +3160,10 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
 }
 
 // CNT: `bins` is the counts array (counts plans): every scan classifies the counts it streams
-template <bool P16, bool FUSED, int FST, bool CNT>
+template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false>
 __global__ __launch_bounds__(SBLOCK) __attribute__((amdgpu_waves_per_eu(4))) void k_scan_w(SCAN_W_ARGS) {
   extern __shared__ double ldsd[];
-  scan_w_small<P16, FUSED, FST, CNT>(ldsd, blockIdx.x, gridDim.x, SCAN_W_PASS);
+  scan_w_small<P16, FUSED, FST, CNT, GATE>(ldsd, blockIdx.x, gridDim.x, SCAN_W_PASS);
 }
 
 // K3 for large grids, one wavefront per window (LDS: the wave's histograms only)
