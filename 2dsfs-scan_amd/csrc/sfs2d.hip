@@ -350,12 +350,19 @@ template <bool B, bool S, bool L, bool N, bool F, bool FS>
 hipError_t launch_prep3(sfs2d_plan* pl) {
   const sfs2d_data* d = pl->data;
   const int par = plan_par(pl);
-  hipExtLaunchKernelGGL((k_prep<B, S, L, N, F, FS>), dim3((unsigned)pl->tiles.size()), dim3(BLOCK1),
-                     (B && L) ? pl->bg_lds : 0, CTX_STREAM(pl->ctx), pl->kev[0], pl->kev[1], 0, pl->K, d->counts, d->pos, d->ann, pl->d_tiles,
-                     pl->d_repl + (size_t)repl_par(pl) * REPL * pl->K.nchrom * pl->K.nh, pl->d_slots, pl->d_bins,
-                     pl->d_bcount + (size_t)par * pl->K.nchrom, pl->d_err, L ? pl->hr : 1,
-                     reinterpret_cast<const double2*>(pl->ctx->d_df + 2 * LNT), pl->d_fsum);
-  return hipGetLastError();
+  auto go = [&](auto kern) {
+    hipExtLaunchKernelGGL(kern, dim3((unsigned)pl->tiles.size()), dim3(BLOCK1),
+                       (B && L) ? pl->bg_lds : 0, CTX_STREAM(pl->ctx), pl->kev[0], pl->kev[1], 0, pl->K, d->counts, d->pos, d->ann, pl->d_tiles,
+                       pl->d_repl + (size_t)repl_par(pl) * REPL * pl->K.nchrom * pl->K.nh, pl->d_slots, pl->d_bins,
+                       pl->d_bcount + (size_t)par * pl->K.nchrom, pl->d_err, L ? pl->hr : 1,
+                       reinterpret_cast<const double2*>(pl->ctx->d_df + 2 * LNT), pl->d_fsum);
+    return hipGetLastError();
+  };
+  // the joint-histogram variant (plan_create sets K.jnt, with hr = 1)
+  if constexpr (B && L && !N && !F && !FS) {
+    if (pl->K.jnt && pl->hr == 1) return go(k_prep<B, S, L, N, F, FS, true>);
+  }
+  return go(k_prep<B, S, L, N, F, FS>);
 }
 
 template <bool B, bool S, bool L, bool N, bool F>
@@ -878,6 +885,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   pl->seg_search = bp && pl->cnt && !pl->do_bg && !pl->seg_synth && !seg_prep;
   pl->K.nm1 = data->n > 0 ? (uint32_t)(data->n - 1) : 0u;
   pl->K.kmul = (uint32_t)(pl->K.n2 + 1) | (1u << 16);
+  pl->K.n2inv = (uint32_t)(0x100000000ull / (uint32_t)(pl->K.n2 + 1)) + 1u;   // n2 + 1 >= 3
   pl->K.n12 = (uint32_t)pl->K.n1 | ((uint32_t)pl->K.n2 << 16);
   pl->K.lim12 = (uint32_t)(pl->K.n1p - 1) | ((uint32_t)(pl->K.n2p - 1) << 16);
   {   // Fst's reciprocals in LDS cover the data's largest called count: the reference counts SNPs whose
@@ -1231,7 +1239,9 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     const char* jev = std::getenv("SFS2D_JNT");
     const size_t jl = pl->bg_lds + (size_t)K.nb2 * 4;
     const bool jwant = jev ? jev[0] == '1' : tileT >= 16384;
-    if (pl->lds_hist && pl->cnt && !kfst && jl + stat <= 64 * 1024 && jwant) {
+    // (one histogram copy per word: the joint path indexes the LDS histogram unreplicated; a counts plan has
+    // no filter, so its histogram pass always launches the JNT instantiation and uses these nb2 words)
+    if (pl->lds_hist && pl->hr == 1 && pl->cnt && !kfst && jl + stat <= 64 * 1024 && jwant) {
       pl->K.jnt = K.nb2;
       pl->bg_lds = jl;
     }

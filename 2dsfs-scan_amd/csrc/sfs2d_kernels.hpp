@@ -142,6 +142,8 @@ struct KParams {
   int ntri;              // k_scan_gw TRI (folded counts plans, n1 = n2 = n): the reachable 2D bins
                          // x1 + x2 <= n, (n+1)(n+2)/2 of them, stored as a triangle (0: full grid)
   int jnt;               // k_prep (counts plans, LDS histogram): the joint (alt1, alt2) histogram, see prep_tile
+                         // (nb2 words of LDS; selects the JNT instantiations at launch)
+  uint32_t n2inv;        // floor(2^32 / (n2+1)) + 1: k / (n2+1) = umulhi(k, n2inv) for k < 2^24 (2D bin -> row)
   int lnl;               // k_scan_gw: ln(x) for x < LNL in the wave's LDS (when it costs no occupancy)
   int nc_ok;             // the data's called counts r + a stay within (n1, n2) in every SNP (known at upload:
                          // max_nc1 <= n1 and max_nc2 <= n2): k_prep's fast steps skip the per-step test for it
@@ -344,6 +346,13 @@ __device__ __forceinline__ double wave_sum_dpp(double v) {
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+}
+
+// v of the lane the DPP control names; a lane without a source lane (wave_shr:1 = 0x138: lane 0,
+// wave_shl:1 = 0x130: lane 63) keeps `old`
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_keep(uint32_t old, uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, 0xf, 0xf, false);
 }
 
 __device__ __forceinline__ uint32_t wave_sum_dpp_u(uint32_t v) {
@@ -649,7 +658,8 @@ __device__ __forceinline__ unsigned long long fst_fixed(double x, double scale) 
 
 // k_prep's work on one tile t (work item ti: its replica is ti % REPL), by a 512-thread workgroup whose
 // dynamic LDS starts at sh_hist
-template <bool DO_BG, bool DO_SEG, bool LDS_HIST, bool DO_BINS, bool FILT, bool FST>
+// JNT: the joint (alt1, alt2) histogram in the common step (below)
+template <bool DO_BG, bool DO_SEG, bool LDS_HIST, bool DO_BINS, bool FILT, bool FST, bool JNT>
 __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32_t ti, uint32_t* sh_hist,
                                           const uint32_t* __restrict__ counts, const uint32_t* __restrict__ pos,
                                           const uint16_t* __restrict__ ann, uint32_t* __restrict__ repl,
@@ -666,14 +676,16 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
   // the exact path (any u8 counts, n <= 510) reads the global table
   __shared__ double2 sh_rcp[FST ? RCPN / 2 : 1];
   __shared__ uint32_t sh_wlo;
-  // JNT (P.jnt = nb2 words, plans whose k_prep only histograms and segments): the common step counts
+  // JNT (nb2 more words of LDS, plans whose k_prep only histograms and segments): the common step counts
   // every SNP once in the joint histogram of its unfolded alt counts (alt1, alt2), laid out as the 2D
   // grid, and a folded SNP once more in the 2D histogram at its (ref1, ref2) key: 1 + (folded) LDS
   // atomics per SNP instead of 3 (2D key, both unfolded 1D spectra).  The tile's end derives both 1D
   // spectra as the joint histogram's margins and adds its bins with alt1 + alt2 <= fold_thr -- the
   // unfolded SNPs' 2D keys -- to the 2D histogram (the edge steps' process() counts the three directly)
-  constexpr bool JNT = DO_BG && LDS_HIST && !DO_BINS && !FST;
-  const bool jnt = JNT && P.jnt != 0;
+  // A compile-time variant, chosen at plan creation with one histogram copy per word (the joint path
+  // indexes sh_hist unreplicated): its common step holds no three-atomic code and no per-SNP branch.
+  static_assert(!JNT || (DO_BG && LDS_HIST && !DO_BINS && !FILT && !FST), "JNT: histogram / segmentation passes only");
+  if (JNT) hr = 1;
   STAMP(20);
   BLK_STAMP(0, 0);
   uint32_t* gh = repl + ((size_t)(ti % REPL) * P.nchrom + t.chrom) * (size_t)P.nh;
@@ -687,8 +699,12 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
     if (threadIdx.x == 0) sh_wlo = DO_SEG ? wid_fast(P, pos[t.begin]) : div_fast(P, t.begin - t.cb);
   }
   if (DO_BG) {
-    if (LDS_HIST)
-      for (int k = threadIdx.x; k < P.nh * hr + WAVE + (JNT ? P.jnt : 0); k += BLOCK1) sh_hist[k] = 0u;
+    if (LDS_HIST) {   // 16-B stores (sh_hist is 16-B aligned), then the last words
+      const int nz = P.nh * hr + WAVE + (JNT ? P.nb2 : 0);
+      uint4* const z4 = reinterpret_cast<uint4*>(sh_hist);
+      for (int k = threadIdx.x; k < (nz >> 2); k += BLOCK1) z4[k] = make_uint4(0u, 0u, 0u, 0u);
+      if ((int)threadIdx.x < (nz & 3)) sh_hist[(nz & ~3) + (int)threadIdx.x] = 0u;
+    }
     if (threadIdx.x == 0) sh_b2 = 0u;
   }
   if (DO_SEG) {
@@ -733,10 +749,14 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
   // wprev / wnext: window ids of the SNPs just before / after the vector.
   // EDGE: the step reaches past the tile (elements outside [t.begin, t.end) are masked);
   // FAST: no lane of the wave holds counts outside the grid (classify_fast)
+  // (not JNT: its common step has its own few, and VGPR copies only process() reads would be live across
+  // the whole step loop)
   KParams Q = P;   // the per-SNP parameters as VGPR copies (vreg)
-  Q.n1 = vreg(P.n1); Q.n2 = vreg(P.n2); Q.n1p = vreg(P.n1p); Q.n2p = vreg(P.n2p); Q.nb2 = vreg(P.nb2);
-  Q.fold_thr = vreg(P.fold_thr); Q.h1a = vreg(P.h1a); Q.h1b = vreg(P.h1b);
-  Q.wmag = vreg(P.wmag); Q.wsh1 = vreg(P.wsh1); Q.wsh2 = vreg(P.wsh2);
+  if (!JNT) {
+    Q.n1 = vreg(P.n1); Q.n2 = vreg(P.n2); Q.n1p = vreg(P.n1p); Q.n2p = vreg(P.n2p); Q.nb2 = vreg(P.nb2);
+    Q.fold_thr = vreg(P.fold_thr); Q.h1a = vreg(P.h1a); Q.h1b = vreg(P.h1b);
+    Q.wmag = vreg(P.wmag); Q.wsh1 = vreg(P.wsh1); Q.wsh2 = vreg(P.wsh2);
+  }
   auto process = [&](auto EDGE_C, auto FAST_C, uint32_t i0, const uint4& cv, const uint4& pv, const uint2& av,
                      uint32_t wprev, uint32_t wnext) {
     constexpr bool EDGE = decltype(EDGE_C)::value, FAST = decltype(FAST_C)::value;
@@ -822,9 +842,9 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
     }
   };
 
-  // one 16-B vector of counts (+ positions) per thread per step; loads are clamped into the tile
-  // (lanes past its end re-read its last vector, masked) so that no load sits behind a branch; the
-  // lanes at the wave edges fetch their neighbour positions in the same batch
+  // one 16-B vector of counts (+ positions) per thread per step, through buffer resources on the tile
+  // (lanes past its end load 0 without an access, masked), so that no load sits behind a branch; one more
+  // load per step fetches the positions next to the wave's SNPs (load_step below)
   // The common step (not a tile's first or last, every count inside the grid, no filter): classify_fast
   // inline with precomputed LDS byte offsets, and window-boundary bookkeeping only in lanes whose
   // neighbours differ.  Everything else goes through process() above.
@@ -848,17 +868,10 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
     bool fm[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const uint32_t c = cc[k];
-      if (JNT && jnt) {
-        if (!(SFS2D_ABL & 64)) {
-          const uint32_t ka = __builtin_amdgcn_udot4(c >> 8, Q.kmul, 0u, false);   // a1 (n2+1) + a2
-          const uint32_t kr = __builtin_amdgcn_udot4(c, Q.kmul, 0u, false);        // r1 (n2+1) + r2
-          const bool sw = (int)__builtin_amdgcn_udot4(c, 0x01000100u, 0u, false) > Q.fold_thr;
-          atomicAdd(ka ? (uint32_t*)((char*)jh_l + (ka << 2)) : trash_p, 1u);
-          atomicAdd((sw & (kr != 0u)) ? (uint32_t*)((char*)hist_l + (kr << 2)) : trash_p, 1u);
-        }
-        continue;
-      }
+      uint32_t c = cc[k];
+      // (opaque: else the byte extracts of all four SNPs, common to process(), are hoisted above the
+      // branch between the two paths and held in ~20 more VGPRs)
+      asm volatile("" : "+v"(c));
       const uint32_t r1 = c & 0xffu, a1 = (c >> 8) & 0xffu, r2 = (c >> 16) & 0xffu, a2 = c >> 24;
       const bool sw = (int)(a1 + a2) > Q.fold_thr;
       const uint32_t x1 = sw ? r1 : a1, x2 = sw ? r2 : a2;
@@ -909,7 +922,53 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
     if (DO_BINS) *reinterpret_cast<uint4*>(bins + i0) = make_uint4(bw[0], bw[1], bw[2], bw[3]);
   };
 
-  constexpr uint32_t STEP = 4 * BLOCK1;
+  // The JNT common step, the lane's four SNPs.  Per SNP: three byte dot products on the counts
+  // word (the joint key a1 (n2+1) + a2, the folded key r1 (n2+1) + r2, and a1 + a2 for the fold), three
+  // compares and two LDS byte addresses; each atomic under its own exec mask, so that key 0 (a fifth of
+  // the SNPs) takes no atomic and there is no trash select.  The keys of all the lane's SNPs come first,
+  // then their atomics: the dot-product chains interleave.  The step reads no spilled scalar.
+  constexpr uint32_t LSNP = 4;           // SNPs per lane and step: one 16-B vector of counts, one of positions
+  typedef __attribute__((address_space(3))) uint32_t lds_u32;
+  const uint32_t kmA = vreg(P.kmul << 8), kmR = P.kmul, fthr = (uint32_t)P.fold_thr;
+  const uint32_t jhb = vreg((uint32_t)(uintptr_t)((lds_u32*)jh_l)), h2b = vreg((uint32_t)(uintptr_t)((lds_u32*)sh_hist));
+  auto jnt_fast = [&](uint32_t i0, const uint4& cv, const uint4& pv, uint32_t wprev, uint32_t wnext) {
+    const uint32_t cc[4] = {cv.x, cv.y, cv.z, cv.w};
+    const uint32_t pp[4] = {pv.x, pv.y, pv.z, pv.w};
+    if (!(SFS2D_ABL & 64)) {   // the four SNPs' 12 dot products, then their atomics
+      uint32_t ka[4], kr[4], sm[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        ka[k] = __builtin_amdgcn_udot4(cc[k], kmA, 0u, false);
+        kr[k] = __builtin_amdgcn_udot4(cc[k], kmR, 0u, false);
+        sm[k] = __builtin_amdgcn_udot4(cc[k], 0x01000100u, 0u, false);
+      }
+      // (else each dot product sinks into its atomic's masked block, one dependent chain per SNP)
+      asm volatile("" : "+v"(ka[0]), "+v"(ka[1]), "+v"(ka[2]), "+v"(ka[3]), "+v"(kr[0]), "+v"(kr[1]), "+v"(kr[2]),
+                        "+v"(kr[3]), "+v"(sm[0]), "+v"(sm[1]), "+v"(sm[2]), "+v"(sm[3]));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (ka[k] != 0u)
+          __hip_atomic_fetch_add((lds_u32*)(uintptr_t)(jhb + (ka[k] << 2)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (((int)sm[k] > (int)fthr) & (kr[k] != 0u))
+          __hip_atomic_fetch_add((lds_u32*)(uintptr_t)(h2b + (kr[k] << 2)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    // window boundaries, as in process_fast: only in lanes whose neighbours' ids differ
+    if (DO_SEG && wprev != wnext) {
+      uint32_t w[LSNP];
+#pragma unroll
+      for (int k = 0; k < (int)LSNP; ++k) w[k] = wid_fast(P, pp[k]);
+#pragma unroll
+      for (int k = 0; k < (int)LSNP; ++k) {
+        const uint32_t qp = k ? w[k - 1] : wprev, qn = k < (int)LSNP - 1 ? w[k + 1] : wnext;
+        uint32_t* sl = reinterpret_cast<uint32_t*>(slots + ((size_t)t.sbase + w[k]));
+        if (qp != w[k]) sl[0] = i0 + k + 1u;
+        if (qn != w[k]) sl[1] = i0 + k + 1u;
+      }
+    }
+  };
+
+  constexpr uint32_t STEP = LSNP * BLOCK1;
   const uint32_t ab = t.begin & ~3u, alast = (t.end - 1u) & ~3u;
   // (a segmentation-only pass -- a supplied background, no bins, no Fst -- reads no counts)
   constexpr bool NEED_C = DO_BG || DO_BINS || FST;
@@ -918,7 +977,7 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
   struct StepIn {
     uint4 c, p;
     uint2 a;
-    uint32_t xp, xn;
+    uint32_t x;   // lanes 0-31: the position before the wave's first SNP, lanes 32-63: the one after its last
   };
   // counts / positions through buffer resources covering the tile's vectors [ab, alast + 4): a load past
   // them (the last step's lanes beyond the tile, the unconditional reload of the step after the last)
@@ -927,43 +986,58 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
   const uint32_t tbytes = (alast + 4u - ab) * 4u;
   const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(counts + ab), (short)0, (int)tbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(pos + ab), (short)0, (int)tbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t chr_rs =   // the chromosome's positions
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(pos + t.cb), (short)0, (int)((t.ce - t.cb) * 4u), 0x00020000);
+  const int lane_off = (int)(LSNP * 4u * threadIdx.x);
+  const uint32_t wave_snp = LSNP * WAVE * (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t xlane_off = lane < WAVE / 2 ? 0u - 4u : LSNP * WAVE * 4u;
   auto load_step = [&](uint32_t base) {
     StepIn x;
-    const uint32_t ia = base + 4 * threadIdx.x;
-    const int off = (int)((ia - ab) * 4u);
+    const int off = (int)(base - ab) * 4 + lane_off;   // the lane's SNPs [ia, ia + LSNP), ia = base + LSNP * thread
     x.c = NEED_C ? __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(crs, off, 0, 0)) : make_uint4(0, 0, 0, 0);
     x.p = need_pos ? __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(prs, off, 0, 0)) : make_uint4(0, 0, 0, 0);
-    x.a = filt ? *reinterpret_cast<const uint2*>(ann + min(ia, alast)) : make_uint2(0, 0);
-    x.xp = 0;
-    x.xn = 0;
-    if (DO_SEG) {   // neighbour positions at the wave edges and past the tile end
-      // (buffer loads on the chromosome's positions, issued by every lane, out of range -- 0, no
-      // access -- where no neighbour is needed: no branch around them, so the count of loads in
-      // flight is the same on every path and a step waits only for its own buffer)
-      const __amdgpu_buffer_rsrc_t pr =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(pos + t.cb), (short)0, (int)((t.ce - t.cb) * 4u), 0x00020000);
-      const uint32_t none = (t.ce - t.cb) * 4u;
-      const bool edge_next = lane == WAVE - 1 || ia + 4 >= t.end;
-      const uint32_t op = (lane == 0 && ia > t.cb) ? (min(ia, alast + 4u) - 1u - t.cb) * 4u : none;
-      const uint32_t on = (edge_next && ia + 4 < t.ce) ? (ia + 4u - t.cb) * 4u : none;
-      x.xp = __builtin_amdgcn_raw_buffer_load_b32(pr, (int)op, 0, 0);
-      x.xn = __builtin_amdgcn_raw_buffer_load_b32(pr, (int)on, 0, 0);
+    x.a = filt ? *reinterpret_cast<const uint2*>(ann + min(base + LSNP * threadIdx.x, alast)) : make_uint2(0, 0);
+    x.x = 0;
+    if (DO_SEG) {
+      // The positions next to the wave's SNPs [wb, wb + 64 LSNP): one buffer load on the chromosome's
+      // positions per step, lanes 0-31 at wb - 1 (lane 0 uses it), lanes 32-63 at wb + 64 LSNP (lane 63
+      // does), so the offset is one add to a wave-uniform scalar.  Out of the chromosome -- before its
+      // first SNP (the offset wraps), past its last, every step past the tile's end -- the load returns 0
+      // with no access.  No branch around it: the count of loads in flight is the same on every path and a
+      // step waits only for its own buffer.  (Edge steps load their neighbours per lane, in body.)
+      // (a step past the tile's end: the resource's size + 4, so that both halves are out of range)
+      const uint32_t wb4 = base < t.end ? (base + wave_snp - t.cb) * 4u : (t.ce - t.cb) * 4u + 4u;   // scalar
+      x.x = __builtin_amdgcn_raw_buffer_load_b32(chr_rs, (int)(wb4 + xlane_off), 0, 0);
     }
     return x;
   };
   // one step of the tile: the SNPs [base, base + STEP), from its loaded vectors
   auto body = [&](uint32_t base, const StepIn& cur) {
-    const uint32_t ia = base + 4 * threadIdx.x;
-    const uint4 ca = cur.c, pa = cur.p;
+    const uint32_t ia = base + LSNP * threadIdx.x;
     const uint2 aav = cur.a;
+    // the masked edge path: a step reaching outside the tile (only a chromosome's first / last tile
+    // has unaligned ends: the host puts tile edges on multiples of 4 SNPs) or
+    // holding the chromosome's first or last SNP (window starts / ends there whatever the neighbours' ids)
+    const bool edge = base < t.begin || base + STEP > t.end || base <= t.cb || base + STEP >= t.ce;   // block-uniform
     uint32_t wpa = 0, wna = 0;
     if (DO_SEG) {
-      const uint32_t xa_prev = cur.xp, xa_next = cur.xn;
-      const bool edge_next = lane == WAVE - 1 || ia + 4 >= t.end;
-      wpa = __shfl_up(wid_fast(P, pa.w), 1, WAVE);
-      wna = __shfl_down(wid_fast(P, pa.x), 1, WAVE);
-      if (lane == 0) wpa = wid_fast(P, xa_prev);
-      if (edge_next) wna = wid_fast(P, xa_next);
+      // the positions before the lane's first SNP and after its last: the neighbour lanes' by DPP wave
+      // shifts (the LDS pipe is the atomics'), which leave lane 0 / lane 63 the step's loaded cur.x
+      uint32_t pprev = dpp_keep<0x138>(cur.x, cur.p.w);   // wave_shr:1
+      uint32_t pnext = dpp_keep<0x130>(cur.x, cur.p.x);   // wave_shl:1
+      if (edge) {   // rare: the lane after the tile's last SNP is masked, so every lane loads its own neighbours
+        const uint32_t none = (t.ce - t.cb) * 4u;
+        const uint32_t ni = ia + LSNP;
+        const bool edge_next = lane == WAVE - 1 || ni >= t.end;
+        const uint32_t op = (lane == 0 && ia > t.cb) ? (min(ia, alast + 4u) - 1u - t.cb) * 4u : none;
+        const uint32_t on = (edge_next && ni < t.ce) ? (ni - t.cb) * 4u : none;
+        const uint32_t xp = __builtin_amdgcn_raw_buffer_load_b32(chr_rs, (int)op, 0, 0);
+        const uint32_t xn = __builtin_amdgcn_raw_buffer_load_b32(chr_rs, (int)on, 0, 0);
+        if (lane == 0) pprev = xp;
+        if (edge_next) pnext = xn;
+      }
+      wpa = wid_fast(P, pprev);
+      wna = wid_fast(P, pnext);
     }
     // counts outside the grid (r + a > n: an error or an out-of-grid key) take the exact classify()
     // (called allele counts r + a by byte dot products)
@@ -972,25 +1046,26 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
     // (P.nc_ok: the upload found no such SNP in the data set; the test -- 8 dot products, 6 max, 2 compares
     // and a ballot per step -- then runs nowhere)
     auto any_bad = [&]() -> bool {
-      const bool bad = (int)(max(max(nc1(ca.x), nc1(ca.y)), max(nc1(ca.z), nc1(ca.w))) > (uint32_t)P.n1) |
-                       (int)(max(max(nc2(ca.x), nc2(ca.y)), max(nc2(ca.z), nc2(ca.w))) > (uint32_t)P.n2);
-      return __ballot(bad) != 0ull;
+      const uint4 ca = cur.c;
+      const uint32_t m1 = max(max(nc1(ca.x), nc1(ca.y)), max(nc1(ca.z), nc1(ca.w)));
+      const uint32_t m2 = max(max(nc2(ca.x), nc2(ca.y)), max(nc2(ca.z), nc2(ca.w)));
+      return __ballot((m1 > (uint32_t)P.n1) | (m2 > (uint32_t)P.n2)) != 0ull;
     };
-    // the masked edge path: a step reaching outside the tile (only a chromosome's first / last tile
-    // has unaligned ends: the host puts tile edges on multiples of 4 SNPs) or holding the
-    // chromosome's first or last SNP (window starts / ends there whatever the neighbours' ids)
-    const bool edge = base < t.begin || base + STEP > t.end || base <= t.cb || base + STEP >= t.ce;   // block-uniform
     using T_ = std::true_type;
     using F_ = std::false_type;
     bool exact = !FASTOK || edge;   // block-uniform; then wave-uniform
-    if (!exact && !P.nc_ok) exact = any_bad();
-    if (exact) process(T_{}, F_{}, ia, ca, pa, aav, wpa, wna);   // exact, masked
+    int nc_ok = P.nc_ok;
+    asm volatile("" : "+s"(nc_ok));   // (tested here as a scalar: hoisted, the test is a 64-bit mask that spills)
+    if (!exact && !nc_ok) exact = any_bad();
+    if (exact) process(T_{}, F_{}, ia, cur.c, cur.p, aav, wpa, wna);   // exact, masked
     else {
 #ifdef SFS2D_MARK
       asm volatile("; HOT_BEGIN");
 #endif
-      if (SFS2D_ABL & 128) asm volatile("" ::"v"(ca.x), "v"(ca.y), "v"(ca.z), "v"(ca.w), "v"(pa.x), "v"(pa.w), "v"(wpa), "v"(wna));
-      else process_fast(ia, ca, pa, wpa, wna);
+      if (SFS2D_ABL & 128)
+        asm volatile("" ::"v"(cur.c.x), "v"(cur.c.y), "v"(cur.c.z), "v"(cur.c.w), "v"(cur.p.x), "v"(cur.p.w), "v"(wpa), "v"(wna));
+      else if constexpr (JNT) jnt_fast(ia, cur.c, cur.p, wpa, wna);
+      else process_fast(ia, cur.c, cur.p, wpa, wna);
 #ifdef SFS2D_MARK
       asm volatile("; HOT_END");
 #endif
@@ -1024,19 +1099,20 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
 #endif
   STAMP(22);
   if (err) atomicOr(err_word, err);
-  if (DO_BG && !jnt) {
+  if (DO_BG && !JNT) {
     b2 = wave_sum_u(b2);
     if (lane == 0 && b2) atomicAdd(&sh_b2, b2);
   }
   if (DO_BG || FST) __syncthreads();
-  if (JNT && jnt) {
+  if (JNT) {
     // the joint histogram's margins into the 1D spectra, its unfolded keys into the 2D bins; the inner
     // 2D count (bins 1 .. nb2-2) from the finished tile histogram (edge-step SNPs included)
+    // (the bin's row k / (n2+1) as a multiply-high: KParams.n2inv)
     const uint32_t n2p1 = (uint32_t)P.n2 + 1u;
     uint32_t bs = 0;
     for (int k = threadIdx.x; k < P.nb2; k += BLOCK1) {
       const uint32_t j = jh_l[k];
-      const uint32_t x1 = (uint32_t)k / n2p1, x2 = (uint32_t)k - x1 * n2p1;
+      const uint32_t x1 = __umulhi((uint32_t)k, P.n2inv), x2 = (uint32_t)k - x1 * n2p1;
       if (j) {
         if (x1) atomicAdd(&sh_hist[P.h1a + (int)x1], j);
         if (x2) atomicAdd(&sh_hist[P.h1b + (int)x2], j);
@@ -1080,7 +1156,7 @@ __device__ __forceinline__ void prep_tile(const KParams& P, const Tile t, uint32
   BLK_STAMP(0, 1);
 }
 
-template <bool DO_BG, bool DO_SEG, bool LDS_HIST, bool DO_BINS, bool FILT, bool FST>
+template <bool DO_BG, bool DO_SEG, bool LDS_HIST, bool DO_BINS, bool FILT, bool FST, bool JNT = false>
 __global__ __launch_bounds__(BLOCK1) void k_prep(KParams P, const uint32_t* __restrict__ counts,
                                                  const uint32_t* __restrict__ pos, const uint16_t* __restrict__ ann,
                                                  const Tile* __restrict__ tiles, uint32_t* __restrict__ repl,
@@ -1088,9 +1164,9 @@ __global__ __launch_bounds__(BLOCK1) void k_prep(KParams P, const uint32_t* __re
                                                  uint32_t* __restrict__ bcount, uint32_t* __restrict__ err_word,
                                                  int hr, const double2* __restrict__ rcp_g,
                                                  unsigned long long* __restrict__ fsum) {
-  extern __shared__ uint32_t sh_hist[];
-  prep_tile<DO_BG, DO_SEG, LDS_HIST, DO_BINS, FILT, FST>(P, tiles[blockIdx.x], blockIdx.x, sh_hist, counts, pos, ann,
-                                                         repl, slots, bins, bcount, err_word, hr, rcp_g, fsum);
+  extern __shared__ __attribute__((aligned(16))) uint32_t sh_hist[];
+  prep_tile<DO_BG, DO_SEG, LDS_HIST, DO_BINS, FILT, FST, JNT>(P, tiles[blockIdx.x], blockIdx.x, sh_hist, counts, pos,
+                                                              ann, repl, slots, bins, bcount, err_word, hr, rcp_g, fsum);
 }
 
 
