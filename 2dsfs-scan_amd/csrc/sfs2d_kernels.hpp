@@ -2258,7 +2258,10 @@ __device__ __forceinline__ void scan_gw_body(double* ldsd, SCAN_W_ARGS) {
       __builtin_amdgcn_sched_barrier(0);
     }
     finish(B, dB);
-    if (!P.fold || filt) {   // rare settings: unfolded (SNPs in the excluded last 2D bin), variant_type filter
+    // rare settings: a SNP can sit in the excluded last 2D bin (n2_all counts it) -- unfolded plans, bins
+    // plans (k_prep's word says so) and over-called data (!nc_ok: a folded key can be (n1, n2)); and the
+    // variant_type filter (nvar).  Folded counts plans of nc_ok data (the triangle's among them) skip it.
+    if (!P.fold || !CNT || !P.nc_ok) {
       for (uint32_t i0 = cur.b; i0 < cur.e; i0 += WAVE) {   // wave-uniform trip count
         const uint32_t w = i0 + lane < cur.e ? snp_word<CNT>(P, bins, i0 + lane) : 0u;
         nlast += __popcll(__ballot((w & B_LAST) != 0u));
@@ -3100,7 +3103,12 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       }
     }
     MARK(22);
-    if (!P.fold || filt) {   // rare settings: unfolded (SNPs in the excluded last 2D bin), variant_type filter
+    // rare settings: a SNP can sit in the excluded last 2D bin (n2_all counts it) -- unfolded plans, bins
+    // plans (k_prep's word says so) and over-called data (!nc_ok: a folded key can be (n1, n2)); and the
+    // variant_type filter (nvar).  Folded counts plans of nc_ok data skip it.  (GATE is chosen for such plans
+    // only and never enters: it tests fold / filt alone, which leaves the benchmarked variants' code and
+    // registers as measured -- without the pass two of them allocate one VGPR less.)
+    if (GATE ? (!P.fold || filt) : (!P.fold || !CNT || !P.nc_ok)) {
       for (uint32_t i0 = cur.b; i0 < cur.e; i0 += WAVE) {   // wave-uniform trip count
         const uint32_t w = i0 + lane < cur.e ? snp_word<CNT>(P, bins, i0 + lane) : 0u;
         nlast += __popcll(__ballot((w & B_LAST) != 0u));

@@ -34,7 +34,7 @@ def _oracle(key, p, fold=True):
     return _REF[key]
 
 
-def _check(recs, fst, ref, n2_all=True):
+def _check(recs, fst, ref):
     from sfs2d import _lib as L
     wins, orec, ofst = ref
     live = (recs["flags"] & L.W_EMPTY) == 0
@@ -45,8 +45,7 @@ def _check(recs, fst, ref, n2_all=True):
     assert len(fl) == len(wins)
     for i, (w, r, o, f) in enumerate(zip(wins, body, orec, ofst)):
         assert (int(r["chrom"]), int(r["begin"]), int(r["end"])) == (w[0], w[2], w[3]), (i, w)
-        for a, b in (("snp_count", "snp_count"), ("n2", "N2"), ("n1a", "N1a"), ("n1b", "N1b")) + \
-                    ((("n2_all", "N2_all"),) if n2_all else ()):
+        for a, b in (("snp_count", "snp_count"), ("n2", "N2"), ("n2_all", "N2_all"), ("n1a", "N1a"), ("n1b", "N1b")):
             assert int(r[a]) == o[b], (i, a, int(r[a]), o[b])
         for a, b in (("t2d", "T2D"), ("t1d_p1", "T1D_p1"), ("t1d_p2", "T1D_p2")):
             v = float(r[a])
@@ -154,16 +153,100 @@ def _overcalled_genome():
 @pytest.mark.parametrize("fold", [True, False])
 def test_overcalled_and_unfolded_take_the_ungated_variant(fold):
     """Over-called counts (max_nc > 2 pop_size at upload) and unfolded plans keep the scan's range test: the
-    SNP in the excluded last bin stays out of n2, and every window matches the oracle.  (n2_all is compared
-    for the unfolded plan only: a folded plan's scan counts no SNP of the last bin, which only over-called
-    data can reach there -- the record's n2_all is then one short of the oracle's, as it was before the
-    variants existed.)"""
+    SNP in the excluded last bin stays out of n2 and is counted in n2_all, and every window matches the
+    oracle, n2_all included: a folded plan's scan counts the last bin's SNPs whenever the data is
+    over-called (only such data can fold a SNP to (n1, n2))."""
     p = _overcalled_genome()
     ref = _oracle(("over", fold), p, fold=fold)
     if fold:
         assert ref[1][0]["N2_all"] == ref[1][0]["N2"] + 1   # the (n1, n2) SNP sits in the first window
     recs, fst = _scan(p, fold=fold, scan_wgs_per_cu=1)
-    _check(recs, fst, ref, n2_all=not fold)
+    _check(recs, fst, ref)
+    if fold:
+        assert int(recs[0]["n2_all"]) == int(recs[0]["n2"]) + 1
+
+
+def _last_bin_window_genome(n1p, n2p, S):
+    """Two chromosomes of ordinary SNPs; SNP S + 1 (inside the second S-SNP window of the first) is
+    over-called so that it folds to (n1, n2), the excluded last bin: (2 n1p, n1p + 1, 2 n2p, n2p)."""
+    from sfs2d.pack import PackedSNPs, pack_counts
+    from sfs2d.synth import synth_genome
+    p = synth_genome(2, [5 * S + 3, 2 * S], n1p, n2p, seed=31 + n1p)
+    counts = p.counts.copy()
+    counts[S + 1] = int(pack_counts(np.array([2 * n1p]), np.array([n1p + 1]), np.array([2 * n2p]), np.array([n2p]))[0])
+    return PackedSNPs(counts, p.pos, p.chrom_off, list(p.chrom_names), p.ann_id, list(p.ann_names), p.pop1, p.pop2)
+
+
+@pytest.mark.parametrize("n1p,n2p,kernel", [(25, 25, "k_scan_w"), (50, 50, "k_scan_gw")])
+def test_last_bin_snp_counts_in_n2_all(n1p, n2p, kernel):
+    """A folded plan's S-SNP window holding one SNP of the excluded last bin among ordinary SNPs:
+    n2_all == n2 + 1 exactly in both fast scans (the rule scan_*_bySNPs skips windows by), every record's
+    integers as the oracle's."""
+    from sfs2d import _lib as L
+    from sfs2d.engine import Engine, ScanConfig
+    S = 70
+    p = _last_bin_window_genome(n1p, n2p, S)
+    ocfg = O.Cfg(n1p, n2p)
+    bgs = O.chrom_backgrounds(p, ocfg)
+    wins = O.snp_windows(p, S)[0]
+    orec = O.window_records(p, wins, ocfg, lambda c: bgs[c])
+    assert orec[1]["N2_all"] == orec[1]["N2"] + 1 and orec[1]["N2"] > 0
+    assert all(o["N2_all"] == o["N2"] for i, o in enumerate(orec) if i != 1)
+    eng = Engine.get(0)
+    dev = eng.upload(p)
+    pl = eng.plan(dev, ScanConfig(n1p=n1p, n2p=n2p, window_mode=L.WINDOW_SNPS, window=S))
+    assert pl.scan_kernel() == kernel
+    pl.run()
+    pl.check()
+    recs = pl.read()
+    pl.close()
+    dev.close()
+    assert len(recs) == len(wins)
+    for i, (w, r, o) in enumerate(zip(wins, recs, orec)):
+        assert (int(r["chrom"]), int(r["begin"]), int(r["end"])) == (w[0], w[-2], w[-1]), (i, w)
+        for a, b in (("snp_count", "snp_count"), ("n2", "N2"), ("n2_all", "N2_all"), ("n1a", "N1a"), ("n1b", "N1b")):
+            assert int(r[a]) == o[b], (i, a, int(r[a]), o[b])
+        for a, b in (("t2d", "T2D"), ("t1d_p1", "T1D_p1"), ("t1d_p2", "T1D_p2")):
+            assert o[b] is not None and gu.close(float(r[a]), o[b]), (i, a, float(r[a]), o[b])
+    assert int(recs[1]["n2_all"]) == int(recs[1]["n2"]) + 1
+
+
+def _bysnp_chrom(last_bin):
+    """One chromosome of 40 polymorphic SNPs at pop 25 / 25, scanned in windows of S = 4; window 5 holds
+    monomorphic SNPs (50, 0, 50, 0) and, with last_bin, the over-called SNP (50, 26, 50, 25), which folds
+    to (n1, n2): the window's 2D SFS then holds one SNP, in the bin bins[1:-1] leaves out."""
+    from sfs2d.pack import PackedSNPs, pack_counts
+    i = np.arange(40)
+    a1, a2 = 1 + (7 * i) % 48, 1 + (11 * i) % 48
+    r1, r2 = 50 - a1, 50 - a2
+    a1[20:24], a2[20:24], r1[20:24], r2[20:24] = 0, 0, 50, 50
+    if last_bin:
+        r1[21], a1[21], r2[21], a2[21] = 50, 26, 50, 25
+    return PackedSNPs(pack_counts(r1, a1, r2, a2), (100 + 37 * i).astype(np.uint32), np.array([0, 40], np.int64),
+                      ["chr0000"], np.zeros(40, np.uint16), ["intergenic_region"], "p1", "p2")
+
+
+def test_bysnps_enters_a_window_of_one_last_bin_snp():
+    """scan_perChr_bySNPs skips a window whose 2D SFS is empty (n2_all == 0).  A window holding only
+    monomorphic SNPs and one SNP of the last bin is entered: T2D is None there and the reference's
+    T2D - T1D_pop1 raises TypeError, as the oracle's."""
+    import twoDSFS_class as T
+    p = _bysnp_chrom(True)
+    with pytest.raises(TypeError):
+        O.scan_perChr_bySNPs(p, 4, O.Cfg(POP, POP))
+    obj = T.LikelihoodInference_jointSFS(None, None, pop1="p1", pop2="p2", pop1_size=POP, pop2_size=POP)
+    with pytest.raises(TypeError):
+        obj.scan_perChr_bySNPs(p, 4)
+
+
+def test_bysnps_skips_a_monomorphic_window():
+    """The same chromosome with window 5 all monomorphic: skipped, the other 9 windows are the oracle's."""
+    import twoDSFS_class as T
+    p = _bysnp_chrom(False)
+    want = O.scan_perChr_bySNPs(p, 4, O.Cfg(POP, POP))
+    assert len(want) == 9
+    obj = T.LikelihoodInference_jointSFS(None, None, pop1="p1", pop2="p2", pop1_size=POP, pop2_size=POP)
+    assert gu.compare_results(obj.scan_perChr_bySNPs(p, 4), want) == []
 
 
 def _fst_edge_chrom(low_nc):
