@@ -7,6 +7,9 @@
 //   k_bg_slice     per-chromosome background tables (skipped for supplied backgrounds)
 //   k_scan_w / _g  bins (4 B/SNP) -> one 64-B record per window slot
 //   k_scan_extra   combined_scan's final-window helper (only with SFS2D_F_PREV_EXTRA)
+// Sliding plans (sfs2d_plan_create_sliding) run k_prep without its segmentation, then k_slots_slide
+// (the overlapping slot table by binary search), the tables, k_fst_win where the scan does not sum
+// Fst itself, and the same scan kernels.
 // All device state a run touches (slot table, background replicas and counters, LDS) is left
 // zeroed by the run itself, so plans replay without memsets.
 #include <hip/hip_runtime.h>
@@ -140,6 +143,8 @@ struct sfs2d_plan {
   bool do_bg = false, do_seg = false, lds_hist = true, bg_ready = false;
   bool seg_synth = false;   // fixed-bp slots from the generator's window offsets (slots_only)
   bool seg_search = false;  // fixed-bp slots by binary search on the positions, k_slots_search (slots_only)
+  int64_t step = 0;         // sliding plan: fixed-bp windows advanced by step bp (0: disjoint windows); its
+                            // slots by k_slots_slide, k_prep without segmentation
   bool fused = false;       // per-chromosome tables built inside k_scan_w (parity-alternating replicas)
   bool sliced = false;      // per-chromosome tables by k_bg_slice without its tail; k_scan_w combines
                             // the leaf sums (parity-alternating inner sums)
@@ -297,11 +302,13 @@ template <bool P16, bool CNT>
 hipError_t launch_scan_c(sfs2d_plan* pl, sfs2d_window* out) {
   const int per_chrom = pl->prm.bg_mode == SFS2D_BG_PER_CHROM ? 1 : 0;
   const int bp = pl->prm.window_mode == SFS2D_WINDOW_BP ? 1 : 0;
+  // (large grids: Fst from k_prep's sums, taken by the scan -- unless window kernels wrote it, fst_win)
+  const bool gfst = pl->fst && !pl->fst_win;
   if (pl->gw) {
     if (CNT && pl->K.ntri) {
-      if (pl->fst) launch_scan_gw<P16, true, CNT, CNT>(pl, out, per_chrom, bp);
+      if (gfst) launch_scan_gw<P16, true, CNT, CNT>(pl, out, per_chrom, bp);
       else launch_scan_gw<P16, false, CNT, CNT>(pl, out, per_chrom, bp);
-    } else if (pl->fst) {
+    } else if (gfst) {
       launch_scan_gw<P16, true, CNT>(pl, out, per_chrom, bp);
     } else {
       launch_scan_gw<P16, false, CNT>(pl, out, per_chrom, bp);
@@ -335,7 +342,7 @@ hipError_t launch_scan_c(sfs2d_plan* pl, sfs2d_window* out) {
       else launch_scan_w<P16, false, false, CNT>(pl, out, per_chrom, bp);
     }
   } else {
-    if (pl->fst) launch_scan_g<P16, true, CNT>(pl, out, per_chrom, bp);
+    if (gfst) launch_scan_g<P16, true, CNT>(pl, out, per_chrom, bp);
     else launch_scan_g<P16, false, CNT>(pl, out, per_chrom, bp);
   }
   return hipGetLastError();
@@ -416,6 +423,32 @@ bool prep_runs(const sfs2d_plan* pl) {
   return !pl->tiles.empty() && (!pl->cnt || pl->do_bg || pl->do_seg || (pl->fst && !pl->fst_win && !pl->fst_scan));
 }
 
+// a sliding plan's slot table (after k_prep, which does not segment for it).  ev: with the k_prep timing
+// events, when the run launches no k_prep (this is then its segmentation stage, as launch_slots_only)
+hipError_t launch_slots_slide(sfs2d_plan* pl, bool ev) {
+  const uint32_t ns = (uint32_t)pl->nslots;
+  if (!ns) return hipSuccess;
+  hipExtLaunchKernelGGL(k_slots_slide, dim3((ns + 255u) / 256u), dim3(256), 0, CTX_STREAM(pl->ctx), ev ? pl->kev[0] : nullptr,
+                        ev ? pl->kev[1] : nullptr, 0, pl->data->pos, pl->data->d_chrom_off, pl->d_slot_base, pl->data->nchrom,
+                        (uint32_t)pl->prm.window, (uint32_t)pl->step, ns, pl->d_slots);
+  return hipGetLastError();
+}
+
+// Fst per slot by k_fst_win (a wavefront per window over the slot table), before the scan: sliding plans
+// whose scan does not sum Fst itself, attached plans of sliced bases
+hipError_t launch_fst_win(sfs2d_plan* a) {
+  const uint32_t ns = (uint32_t)a->nslots;
+  if (!ns) return hipSuccess;
+  const dim3 gf((unsigned)std::min<uint32_t>(2048u, (ns + 3u) / 4u));
+  if (a->cnt)
+    hipLaunchKernelGGL(k_fst_win<true>, gf, dim3(256), 0, CTX_STREAM(a->ctx), a->K, a->data->counts, scan_src(a), a->d_slots,
+                       reinterpret_cast<const double2*>(a->ctx->d_df + 2 * LNT), a->d_fst, ns);
+  else
+    hipLaunchKernelGGL(k_fst_win<false>, gf, dim3(256), 0, CTX_STREAM(a->ctx), a->K, a->data->counts, scan_src(a), a->d_slots,
+                       reinterpret_cast<const double2*>(a->ctx->d_df + 2 * LNT), a->d_fst, ns);
+  return hipGetLastError();
+}
+
 hipError_t launch_prep(sfs2d_plan* pl, bool bins) {
   if (pl->tiles.empty()) return hipSuccess;
   const bool L = pl->lds_hist;
@@ -472,22 +505,17 @@ hipError_t launch_attached(sfs2d_plan* a) {
   const uint32_t ns = (uint32_t)a->nslots;
   if (!ns) { a->runs++; return hipSuccess; }
   const dim3 g((ns + 255) / 256);
-  if (a->prm.window_mode == SFS2D_WINDOW_BP)
+  if (a->step)
+    hipLaunchKernelGGL(k_slots_slide, g, dim3(256), 0, CTX_STREAM(a->ctx), d->pos, d->d_chrom_off, a->d_slot_base,
+                       d->nchrom, (uint32_t)a->prm.window, (uint32_t)a->step, ns, a->d_slots);
+  else if (a->prm.window_mode == SFS2D_WINDOW_BP)
     hipLaunchKernelGGL(k_slots_bp, g, dim3(256), 0, CTX_STREAM(a->ctx), d->pos, d->d_chrom_off, a->d_slot_base,
                        d->nchrom, (uint32_t)a->prm.window, ns, a->d_slots);
   if (a->fst_m)
     hipLaunchKernelGGL(k_fst_agg, g, dim3(256), 0, CTX_STREAM(a->ctx), a->base->d_fsum, a->base->d_slot_base,
                        a->d_slot_base, d->nchrom, a->fst_m, ns,
                        std::max(0, a->base->K.fst_e - a->K.fst_e), a->d_fsum);
-  if (a->fst_win) {   // before the scan clears the slots
-    const dim3 gf((unsigned)std::min<uint32_t>(2048u, (ns + 3u) / 4u));
-    if (a->cnt)
-      hipLaunchKernelGGL(k_fst_win<true>, gf, dim3(256), 0, CTX_STREAM(a->ctx), a->K, d->counts, scan_src(a), a->d_slots,
-                         reinterpret_cast<const double2*>(a->ctx->d_df + 2 * LNT), a->d_fst, ns);
-    else
-      hipLaunchKernelGGL(k_fst_win<false>, gf, dim3(256), 0, CTX_STREAM(a->ctx), a->K, d->counts, scan_src(a), a->d_slots,
-                         reinterpret_cast<const double2*>(a->ctx->d_df + 2 * LNT), a->d_fst, ns);
-  }
+  if (a->fst_win) launch_fst_win(a);   // before the scan clears the slots
   const hipError_t e = launch_scan_any(a, a->d_out);
   a->last_out = a->d_out;
   a->runs++;
@@ -809,15 +837,38 @@ static int make_kparams(sfs2d_ctx* ctx, const sfs2d_params* prm, int nchrom, KPa
   return 0;
 }
 
-static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, int force_sliced,
+static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, int force_sliced, int64_t step,
                        sfs2d_plan** out);
 
 int sfs2d_plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, sfs2d_plan** out) {
-  return plan_create(ctx, data, prm, -1, out);
+  return plan_create(ctx, data, prm, -1, 0, out);
+}
+
+// a sliding plan's step against its params (after make_kparams accepted them)
+static int check_step(sfs2d_ctx* ctx, const sfs2d_params* prm, int64_t step) {
+  if (prm->window_mode != SFS2D_WINDOW_BP) return set_err(ctx, SFS2D_E_ARG, "sliding windows need fixed-bp windows (SFS2D_WINDOW_BP)");
+  if (step < 1 || step > prm->window) return set_err(ctx, SFS2D_E_ARG, "step must be in [1, window]");
+  if (prm->window % step != 0) return set_err(ctx, SFS2D_E_ARG, "step must divide the window");
+  if (prm->window / step > 64) return set_err(ctx, SFS2D_E_ARG, "window / step must be <= 64");
+  if (prm->flags & SFS2D_F_PREV_EXTRA)
+    return set_err(ctx, SFS2D_E_ARG, "SFS2D_F_PREV_EXTRA (quirk Q9 of the disjoint window loop) is not defined for sliding windows");
+  return 0;
+}
+
+int sfs2d_plan_create_sliding(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, int64_t step,
+                              sfs2d_plan** out) {
+  if (!ctx || !data || !prm || !out) return set_err(ctx, SFS2D_E_ARG, "null argument");
+  *out = nullptr;
+  KParams K;
+  int rc = make_kparams(ctx, prm, data->nchrom, &K);
+  if (!rc) rc = check_step(ctx, prm, step);
+  // step == window is the disjoint geometry: the ordinary plan itself (records and Fst byte-equal by construction)
+  return rc ? rc : plan_create(ctx, data, prm, -1, step == prm->window ? 0 : step, out);
 }
 
 // force_sliced: -1 choose (windows per wave), 0 fused, 1 sliced (attached plans follow their base)
-static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, int force_sliced,
+// step: 0 disjoint windows; > 0 a sliding plan (checked by check_step)
+static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, int force_sliced, int64_t step,
                        sfs2d_plan** out) {
   if (!ctx || !data || !prm || !out) return set_err(ctx, SFS2D_E_ARG, "null argument");
   *out = nullptr;
@@ -825,13 +876,16 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   KParams K;
   int rc = make_kparams(ctx, prm, data->nchrom, &K);
   if (rc) return rc;
+  const bool slide = step > 0;
+  const int64_t adv = slide ? step : prm->window;   // bp from one window's start to the next's
   sfs2d_plan* pl = new sfs2d_plan();
   pl->ctx = ctx; pl->data = data; pl->prm = *prm; pl->K = K;
   // no SNP of the data set has more called alleles than 2 pop_size in either population (max_nc1 / max_nc2)
   const bool nc_ok = data->max_nc1 <= (uint32_t)K.n1 && data->max_nc2 <= (uint32_t)K.n2;
   pl->K.nc_ok = nc_ok ? 1 : 0;
   const bool bp = prm->window_mode == SFS2D_WINDOW_BP;
-  pl->do_seg = bp;
+  pl->step = slide ? step : 0;
+  pl->do_seg = bp && !slide;   // (a sliding plan's slots: k_slots_slide after k_prep)
   pl->do_bg = prm->bg_mode == SFS2D_BG_PER_CHROM;
   pl->nbg = pl->do_bg ? std::max(1, data->nchrom) : 1;
   const int nc = data->nchrom;
@@ -844,7 +898,8 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     const int64_t len = data->chrom_off[c + 1] - data->chrom_off[c];
     int64_t ns = 0;
     if (len > 0) {
-      if (bp) ns = (int64_t)(data->last_pos[c] ? (data->last_pos[c] - 1u) / (uint32_t)prm->window : 0u) + 1;
+      // (sliding: slot j starts at j step + 1, the last one holds the chromosome's last SNP)
+      if (bp) ns = (int64_t)(data->last_pos[c] ? (data->last_pos[c] - 1u) / (uint32_t)adv : 0u) + 1;
       else ns = len / prm->window;
       last_c = (uint32_t)c;
       any = true;
@@ -872,7 +927,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // offsets: what a real replicate VCF gets); both are selected by tests/test_synth_device.py
   const char* seg_ev = std::getenv("SFS2D_SEG");
   const bool seg_prep = seg_ev && std::strcmp(seg_ev, "prep") == 0, seg_srch = seg_ev && std::strcmp(seg_ev, "search") == 0;
-  if (bp && data->d_win_off && (uint32_t)prm->window == data->win_bp && pl->cnt && !pl->do_bg &&
+  if (bp && !slide && data->d_win_off && (uint32_t)prm->window == data->win_bp && pl->cnt && !pl->do_bg &&
       pl->nslots == (int64_t)nc * (int64_t)data->win_per_chrom) {
     bool all = true;
     for (int c = 0; c < nc && all; ++c) all = data->chrom_off[c + 1] > data->chrom_off[c];
@@ -882,7 +937,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // k_prep cost more than the positions it saved k_prep -- config 3: k_prep 83.5 -> 64.5 us but one pass
   // 0.214 -> 0.225 ms, the overlapped step 0.184 -> 0.191 ms, config 2 2.4e8 -> 2.0e8 windows/s; as extra
   // blocks of k_prep itself, concurrent with its tiles: 0.185 -> 0.193 ms; profiles/r06e_*, r06f_*.)
-  pl->seg_search = bp && pl->cnt && !pl->do_bg && !pl->seg_synth && !seg_prep;
+  pl->seg_search = bp && !slide && pl->cnt && !pl->do_bg && !pl->seg_synth && !seg_prep;
   pl->K.nm1 = data->n > 0 ? (uint32_t)(data->n - 1) : 0u;
   pl->K.kmul = (uint32_t)(pl->K.n2 + 1) | (1u << 16);
   pl->K.n2inv = (uint32_t)(0x100000000ull / (uint32_t)(pl->K.n2 + 1)) + 1u;   // n2 + 1 >= 3
@@ -915,6 +970,14 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     for (int c = 0; c < nc; ++c) {
       int64_t run = 0;
       uint32_t pw = 0xffffffffu;
+      if (slide) {   // a bound: the most SNPs in any ws bp that start at an SNP (every sliding window lies in one)
+        int64_t j = data->chrom_off[c];
+        for (int64_t i = data->chrom_off[c]; i < data->chrom_off[c + 1]; ++i) {
+          while ((int64_t)data->host_pos[i] - (int64_t)data->host_pos[j] >= prm->window) ++j;
+          longest = std::max(longest, i - j + 1);
+        }
+        continue;
+      }
       for (int64_t i = data->chrom_off[c]; i < data->chrom_off[c + 1]; ++i) {
         const uint32_t p = data->host_pos[i];
         const uint32_t w = p ? (p - 1u) / (uint32_t)prm->window : 0u;
@@ -1069,7 +1132,10 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   const PwTree pw = pw_plan(K.nb2 - 3);
   pl->fst_mask = data->low_nc;
   pl->fst_win = pl->sliced && bp && pl->fst && !pl->fst_scan;
-  pl->nfst = pl->fst_win ? (int)std::min<int64_t>(1024, std::max<int64_t>(1, (pl->nslots + 7) / 8)) : 0;   // ~1 window per wave
+  // a sliding plan has no k_prep sums (they are per disjoint window): Fst where the scan does not sum it is
+  // k_fst_win over the sliding slots, launched on its own before the scan
+  if (slide) pl->fst_win = pl->fst && !pl->fst_scan;
+  pl->nfst = pl->fst_win && !slide ? (int)std::min<int64_t>(1024, std::max<int64_t>(1, (pl->nslots + 7) / 8)) : 0;   // ~1 window per wave
   if (pl->scan_lds > 64 * 1024) {
     const int lds = (int)pl->scan_lds;
     const hipFuncAttribute A = hipFuncAttributeMaxDynamicSharedMemorySize;
@@ -1315,7 +1381,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   rc = rc ? rc : dalloc(ctx, &pl->d_err, 4);
   if (pl->fst) rc = rc ? rc : dalloc(ctx, &pl->d_fst, (size_t)pl->nslots + 1);
   pl->d_fst_own = pl->d_fst;
-  if (pl->seg_search && !rc) {   // k_slots_search's slot bases per chromosome (u32: nslots < 2^31)
+  if ((pl->seg_search || slide) && !rc) {   // k_slots_search's / k_slots_slide's slot bases per chromosome (u32: nslots < 2^31)
     std::vector<uint32_t> sb(pl->slot_base_h.begin(), pl->slot_base_h.end());
     rc = dalloc(ctx, &pl->d_slot_base, sb.size());
     if (!rc && hipMemcpy(pl->d_slot_base, sb.data(), sizeof(uint32_t) * sb.size(), hipMemcpyHostToDevice) != hipSuccess)
@@ -1407,12 +1473,15 @@ int sfs2d_plan_run_phase(sfs2d_plan* pl, int phase, sfs2d_window* out_dev) {
       if (pl->nslots == 0 && (rc = mark(0))) return rc;
     } else {
       HIPCHK(ctx, launch_prep(pl, true));
-      if (!prep_runs(pl) && (rc = mark(0))) return rc;
+      const bool slots = pl->step && pl->nslots;   // a sliding plan's table, after k_prep
+      if (slots) HIPCHK(ctx, launch_slots_slide(pl, !prep_runs(pl)));
+      if (!prep_runs(pl) && !slots && (rc = mark(0))) return rc;
     }
   }
   if (phase == 0 || phase == 2) {
     if (pl->do_bg && !pl->fused) HIPCHK(ctx, launch_bg_slices(pl));
     else if ((rc = mark(2))) return rc;
+    if (pl->step && pl->fst_win) HIPCHK(ctx, launch_fst_win(pl));   // (the scan may clear the slots)
     for (sfs2d_plan* a : pl->attached) HIPCHK(ctx, launch_attached(a));   // before the base clears its state
     sfs2d_window* out = out_dev ? out_dev : pl->d_out;
     if (pl->chunks.empty() && (rc = mark(4))) return rc;
@@ -1822,8 +1891,10 @@ int sfs2d_plan_time(sfs2d_plan* pl, int iters, double* ms_run, double* ms_k1, do
   for (int it = 0; it < iters; ++it) {
     HIPCHK(ctx, hipEventRecord(pl->ev[0], st));
     HIPCHK(ctx, slots_only(pl) ? launch_slots_only(pl) : launch_prep(pl, true));
+    if (pl->step) HIPCHK(ctx, launch_slots_slide(pl, false));
     HIPCHK(ctx, hipEventRecord(pl->ev[1], st));
     if (pl->do_bg && !pl->fused) HIPCHK(ctx, launch_bg_slices(pl));
+    if (pl->step && pl->fst_win) HIPCHK(ctx, launch_fst_win(pl));
     for (sfs2d_plan* a : pl->attached) HIPCHK(ctx, launch_attached(a));
     HIPCHK(ctx, hipEventRecord(pl->ev[2], st));
     HIPCHK(ctx, launch_scan_any(pl, pl->d_out));
@@ -1864,7 +1935,28 @@ int sfs2d_plan_destroy(sfs2d_plan* pl) {
   return 0;
 }
 
+static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, sfs2d_plan** out);
+
 int sfs2d_plan_attach(sfs2d_plan* base, const sfs2d_params* prm, sfs2d_plan** out) {
+  return plan_attach(base, prm, 0, out);
+}
+
+int sfs2d_plan_attach_sliding(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, sfs2d_plan** out) {
+  if (!base || !prm || !out) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = base->ctx;
+  *out = nullptr;
+  KParams K;
+  int rc = make_kparams(ctx, prm, base->data->nchrom, &K);
+  if (!rc) rc = check_step(ctx, prm, step);
+  if (rc) return rc;
+  // step == window is the disjoint geometry: the ordinary attached plan (byte-equal by construction), unless
+  // it is refused for its Fst rule alone -- a sliding plan's Fst needs no sums of the base
+  if (step == prm->window && plan_attach(base, prm, 0, out) == 0) return 0;
+  return plan_attach(base, prm, step, out);
+}
+
+// step: 0 an ordinary attached plan; > 0 a sliding one (checked by check_step)
+static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, sfs2d_plan** out) {
   if (!base || !prm || !out) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = base->ctx;
   *out = nullptr;
@@ -1879,7 +1971,7 @@ int sfs2d_plan_attach(sfs2d_plan* base, const sfs2d_params* prm, sfs2d_plan** ou
     return set_err(ctx, SFS2D_E_ARG, "an attached plan may differ from its base only in the window and flags");
   const bool bp = prm->window_mode == SFS2D_WINDOW_BP;
   sfs2d_plan* a = nullptr;
-  int rc = plan_create(ctx, base->data, prm, base->sliced ? 1 : 0, &a);
+  int rc = plan_create(ctx, base->data, prm, base->sliced ? 1 : 0, step, &a);
   if (rc) return rc;
   if (a->fused != base->fused || a->sliced != base->sliced || a->G != base->G || a->cnt != base->cnt) {
     plan_free(a); delete a;
@@ -1888,11 +1980,12 @@ int sfs2d_plan_attach(sfs2d_plan* base, const sfs2d_params* prm, sfs2d_plan** ou
   // Fst of an attached plan: its own scan's sums (fst_scan), else the base's k_prep sums added per
   // attached window (fused bases) or k_fst_win on the attached slots (sliced bases)
   uint32_t m = 0;
-  if ((prm->flags & SFS2D_F_FST) && !a->fst_scan) {
+  // (a sliding attached plan: its own k_fst_win, whatever the base; a sliding base has no k_prep sums to add)
+  if ((prm->flags & SFS2D_F_FST) && !a->fst_scan && !step) {
     const bool base_bp = b.window_mode == SFS2D_WINDOW_BP;
     const char* why = nullptr;
     if (!bp) why = "attached Fst needs fixed-bp windows";
-    else if (!base->sliced && (!(b.flags & SFS2D_F_FST) || base->fst_scan || !base_bp || prm->window % b.window != 0))
+    else if (!base->sliced && (!(b.flags & SFS2D_F_FST) || base->fst_scan || base->fst_win || !base_bp || prm->window % b.window != 0))
       why = "attached Fst needs a fixed-bp Fst base plan whose window divides this one's";
     if (why) { plan_free(a); delete a; return set_err(ctx, SFS2D_E_ARG, why); }
     if (!base->sliced) m = (uint32_t)(prm->window / b.window);
@@ -1917,11 +2010,11 @@ int sfs2d_plan_attach(sfs2d_plan* base, const sfs2d_params* prm, sfs2d_plan** ou
   }
   a->base = base;
   a->fst_m = m;
-  a->fst_win = base->sliced && (prm->flags & SFS2D_F_FST) && !a->fst_scan;   // k_fst_win on the attached slots
+  a->fst_win = (base->sliced || step) && (prm->flags & SFS2D_F_FST) && !a->fst_scan;   // k_fst_win on the attached slots
   a->nfst = 0;
   rc = 0;
   std::vector<uint32_t> sb(a->slot_base_h.begin(), a->slot_base_h.end());
-  rc = rc ? rc : dalloc(ctx, &a->d_slot_base, sb.size());
+  if (!a->d_slot_base) rc = rc ? rc : dalloc(ctx, &a->d_slot_base, sb.size());
   if (m && !base->d_slot_base) {
     std::vector<uint32_t> bsb(base->slot_base_h.begin(), base->slot_base_h.end());
     rc = rc ? rc : dalloc(ctx, &base->d_slot_base, bsb.size());

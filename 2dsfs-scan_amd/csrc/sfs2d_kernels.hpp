@@ -3430,6 +3430,32 @@ __global__ __launch_bounds__(256) void k_slots_search(const uint32_t* __restrict
   if (s < nslots) slots[s] = b < e ? make_uint2(b + 1u, e) : make_uint2(0u, 0u);
 }
 
+// The slot table of a sliding plan (sfs2d_plan_create_sliding / _attach_sliding): windows of ws bp
+// advanced by `step` bp (ws % step == 0).  Slot j of chromosome c holds the SNPs with
+// j step + 1 <= pos <= j step + ws: begin = the first SNP with pos >= j step + 1 (slot 0: the
+// chromosome's first SNP, so pos 0 lands in slot 0 only, as wid_of), end = the first SNP with
+// pos >= j step + ws + 1; all bounds in 64 bits.  One thread per slot, two searches (the slots overlap,
+// so a slot's end is not its neighbour's begin unless step == ws).  Every slot is written every run,
+// empty ones as (0, 0): no scan kernel has to clear the table.  With step == ws the table is k_slots_bp's.
+__global__ __launch_bounds__(256) void k_slots_slide(const uint32_t* __restrict__ pos, const long long* __restrict__ chrom_off,
+                                                     const uint32_t* __restrict__ slot_base, int nchrom, uint32_t ws,
+                                                     uint32_t step, uint32_t nslots, uint2* __restrict__ slots) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= nslots) return;
+  int lo = 0, hi = nchrom;   // chromosome c with slot_base[c] <= s < slot_base[c+1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (slot_base[mid] <= s) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t j = s - slot_base[lo];
+  const uint32_t cb = (uint32_t)chrom_off[lo], ce = (uint32_t)chrom_off[lo + 1];
+  const unsigned long long p0 = (unsigned long long)j * step;
+  const uint32_t b = j ? lower_bound_pos(pos, cb, ce, p0 + 1ull) : cb;
+  const uint32_t e = lower_bound_pos(pos, b, ce, p0 + (unsigned long long)ws + 1ull);
+  slots[s] = b < e ? make_uint2(b + 1u, e) : make_uint2(0u, 0u);
+}
+
 // Fst sums of an attached fixed-bp plan whose window is m times the base plan's: window j of
 // chromosome c is base windows [j*m, (j+1)*m) of c, and the base's int64 fixed-point sums add
 // exactly (the same value as k_prep accumulating the attached windows directly).

@@ -15,6 +15,9 @@ columns; ``--fst`` appends an ``FST`` column with this framework's Hudson estima
 ``--pixy-fst FILE`` instead joins pixy's ``avg_wc_fst`` by (chromosome, window_start,
 window_end) the way ECBstats_plots.R:16-41 does (pixy chromosome ``NC_087088_1`` -> ``NC_087088.1``)
 -- the FST column of the published data/ECBstats_*.csv.
+
+``--step BP`` makes every ``--window`` a sliding scan (windows advanced by BP, a divisor of each window;
+multi_sliding_scan): ``<prefix>_20kb_step5kb.csv`` with the same columns, clean None rules.
 """
 from __future__ import annotations
 
@@ -72,6 +75,8 @@ def main(argv=None):
     ap.add_argument("--pop2-size", type=int, default=14)
     ap.add_argument("--window", type=int, action="append", default=[], help="fixed-bp window (combined_scan)")
     ap.add_argument("--snp-window", type=int, action="append", default=[], help="SNPs per window (scan_perChr_bySNPs)")
+    ap.add_argument("--step", type=int, default=None, metavar="BP",
+                    help="sliding windows: advance every --window by BP (a divisor of it, >= window / 64)")
     ap.add_argument("--variant-type", default=None)
     ap.add_argument("--no-fold", action="store_true")
     ap.add_argument("--chromosomes", default=None, help="accession<TAB>number map (chromosomes.txt)")
@@ -83,6 +88,16 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if not a.window and not a.snp_window:
         a.window = [20000]
+    if a.step is not None:
+        if a.snp_window:
+            ap.error("--step applies to fixed-bp windows: not with --snp-window")
+        if a.step < 1:
+            ap.error("--step must be >= 1")
+        for ws in a.window:
+            if ws < a.step or ws % a.step != 0:
+                ap.error(f"--step {a.step} does not divide --window {ws}")
+            if ws // a.step > 64:
+                ap.error(f"--window {ws} is more than 64 steps of {a.step}")
 
     import twoDSFS_class as T
     from sfs2d.vcf import make_packed_vcf
@@ -98,6 +113,17 @@ def main(argv=None):
                                          device=a.device)
     outs = []
     t = time.perf_counter()
+    if a.step is not None:   # sliding windows: every size from one upload and one k_prep pass
+        res = obj.multi_sliding_scan(packed, a.window, a.step, fst=a.fst)
+        print(f"multi_sliding_scan ({len(a.window)} window sizes, step {a.step}): {time.perf_counter() - t:.2f} s",
+              file=sys.stderr)
+        for ws in a.window:
+            path = f"{a.out_prefix}_{_fmt_kb(ws)}_step{_fmt_kb(a.step)}.csv"
+            rows = res[ws]
+            write_csv(path, rows, chr_ids, {k: r["FST"] for k, r in rows.items()} if a.fst else None, pixy)
+            outs.append(path)
+            print(f"sliding_scan {ws} bp / {a.step} bp: {len(rows)} windows -> {path}", file=sys.stderr)
+        return outs
     # every window size from one k_prep pass over the resident stream (sfs2d_plan_attach)
     res = obj.multi_scan(packed, a.window, a.snp_window, fst=a.fst)
     print(f"multi_scan ({len(a.window)} bp + {len(a.snp_window)} SNP-count window sizes): "

@@ -30,6 +30,8 @@ class ScanConfig:
     prev_extra: bool = False
     fst: bool = False          # also compute Hudson's Fst per window slot (Plan.read_fst)
     scan_wgs_per_cu: int = 0   # cap on scan workgroups per CU (0: all that fit; see sfs2d_params)
+    step: Optional[int] = None   # sliding windows: fixed-bp windows advanced by `step` bp (None: disjoint windows);
+                                 # not part of params(): Engine.plan / Plan.attach pass it to the sliding entry points
 
     def params(self) -> L.Params:
         p = L.Params()
@@ -194,16 +196,22 @@ class Plan:
         self.h = C.c_void_p()
         self.attached = []
         prm = cfg.params()
-        if base is None:
+        if base is None and cfg.step is None:
             eng.check(eng.lib.sfs2d_plan_create(eng.h, data.h, C.byref(prm), C.byref(self.h)))
-        else:
+        elif base is None:
+            eng.check(eng.lib.sfs2d_plan_create_sliding(eng.h, data.h, C.byref(prm), int(cfg.step), C.byref(self.h)))
+        elif cfg.step is None:
             eng.check(eng.lib.sfs2d_plan_attach(base.h, C.byref(prm), C.byref(self.h)))
+        else:
+            eng.check(eng.lib.sfs2d_plan_attach_sliding(base.h, C.byref(prm), int(cfg.step), C.byref(self.h)))
+        if base is not None:
             base.attached.append(self)
         self.nrec = int(eng.lib.sfs2d_plan_num_records(self.h))
 
     def attach(self, cfg: ScanConfig) -> "Plan":
-        """A plan scanned from this plan's k_prep pass (another window size / SNP-count windows):
-        run this (base) plan, then read the attached one (sfs2d_plan_attach)."""
+        """A plan scanned from this plan's k_prep pass (another window size / SNP-count windows, or with
+        ``cfg.step`` sliding windows): run this (base) plan, then read the attached one
+        (sfs2d_plan_attach / sfs2d_plan_attach_sliding)."""
         return Plan(self.eng, self.data, cfg, base=self)
 
     def set_background(self, bg2d, bg1a, bg1b):

@@ -127,6 +127,30 @@ def fixed_bg_scan(recs, packed, ws, nslots):
     return res
 
 
+def sliding_scan(recs, packed, ws, step, fst=None):
+    """Rows of a sliding plan (sfs2d_plan_create_sliding: windows of ``ws`` bp advanced by ``step``):
+    {"<chrom> <j*step+1>-<j*step+ws>": row} per non-empty slot, in slot order, each row with the seven
+    keys of combined_scan, plus "FST" (None for NaN) when ``fst`` (the plan's Fst per slot) is given.
+    Clean semantics, not the reference driver's: a statistic is None where the window's N or the
+    background's B is 0 (``_v``), the derived terms T2D - T1D_popK and T2D - (T1D_pop1 + T1D_pop2) / 2 are
+    None when an input is None -- no stale carry (Q6), no final block (Q9), no TypeError."""
+    names = packed.chrom_names
+    res = {}
+    for i, r in enumerate(recs):
+        if r["flags"] & (L.W_EMPTY | L.W_EXTRA):
+            continue
+        T2D, T1, T2 = _v(r, 2), _v(r, 1), _v(r, 0)
+        s = 1 + int(r["wid"]) * step
+        row = {"snp_count": int(r["snp_count"]), "T2D": T2D, "T1D_pop1": T1, "T1D_pop2": T2,
+               "new_term_pop1": None if T2D is None or T1 is None else T2D - T1,
+               "new_term_pop2": None if T2D is None or T2 is None else T2D - T2,
+               "T2D_diff": None if T2D is None or T1 is None or T2 is None else T2D - (T1 + T2) / 2}
+        if fst is not None:
+            row["FST"] = None if np.isnan(fst[i]) else float(fst[i])
+        res[f"{names[int(r['chrom'])]} {s}-{s + ws - 1}"] = row
+    return res
+
+
 def single_stat_scan(recs, packed, ws, nslots, which, name):
     """T1D_scan (539-623) / T2D_scan (686-776): {label: {"snp_count", name}} per non-empty fixed-bp
     window, the statistic None for an empty window or background (no guard, no derived terms).

@@ -327,6 +327,90 @@ class LikelihoodInference_jointSFS:
                     out.setdefault("fst", {})[w] = self.window_fst(p, window_size=w)
         return out
 
+    # ------------------------------------------------------------------ sliding windows (extension)
+    @staticmethod
+    def _check_steps(window_sizes, step_size):
+        """The sliding geometry's rules (sfs2d_plan_create_sliding), checked before any GPU work."""
+        step = int(step_size)
+        if step < 1:
+            raise ValueError(f"step_size must be >= 1, got {step_size}")
+        for w in window_sizes:
+            if int(w) < step or int(w) % step != 0:
+                raise ValueError(f"step_size {step} does not divide window size {w}")
+            if int(w) // step > 64:
+                raise ValueError(f"window size {w} is more than 64 steps of {step}")
+        return step
+
+    def sliding_scan(self, data_dict, window_size, step_size, background_chromosome=None, fst=False):
+        """Overlapping fixed-bp windows: ``window_size`` bp advanced by ``step_size`` bp (a divisor of the
+        window, at most 64 steps per window; sfs2d_plan_create_sliding).  The reference has no such scan:
+        its script scans at 20 kb and at 500 kb and compares (twoDSFS_class.py:1923-1932) because a signal on
+        an edge of its disjoint windows is split between two of them.  ``background_chromosome`` None: each
+        chromosome is its own background (as combined_scan); else that chromosome's SFS for every window (as
+        scan_chooseChr).  Returns {"<chrom> <start>-<end>": row} per non-empty window with combined_scan's
+        seven keys, plus "FST" (Hudson's, as window_fst) when ``fst``; clean None rules (post.sliding_scan)."""
+        if self.distributed:
+            raise NotImplementedError("sliding_scan is single-GPU (distributed sharding of sliding windows is not implemented)")
+        ws = int(window_size)
+        step = self._check_steps([ws], step_size)
+        p = self._pack(data_dict)
+        bg = None
+        if background_chromosome is not None:
+            if background_chromosome not in p.chrom_names:
+                raise ValueError(f"Background chromosome {background_chromosome} not found in the data.")
+            bg = self._bg_arrays(p, p.chrom_names.index(background_chromosome))
+        cfg = self._cfg(p, window_mode=L.WINDOW_BP, window=ws, fst=bool(fst), step=step,
+                        bg_mode=L.BG_PER_CHROM if bg is None else L.BG_SUPPLIED)
+        eng = self._engine()
+        dev = eng.upload(p)
+        try:
+            pl = eng.plan(dev, cfg)
+            try:
+                if bg is not None:
+                    pl.set_background(*bg)
+                pl.run()
+                pl.check()
+                recs = pl.read()
+                f = pl.read_fst() if fst else None
+            finally:
+                pl.close()
+        finally:
+            dev.close()
+        return post.sliding_scan(recs, p, ws, step, f)
+
+    def multi_sliding_scan(self, data_dict, window_sizes, step_size, fst=False):
+        """sliding_scan (per-chromosome backgrounds) at every size in ``window_sizes`` with one step, from
+        ONE upload and one k_prep pass: the smallest window is a sliding plan of its own, the others are
+        attached to it (sfs2d_plan_attach_sliding).  Returns {window_size: sliding_scan rows}.  A window the
+        step does not divide raises ValueError before any GPU work."""
+        if self.distributed:
+            raise NotImplementedError("multi_sliding_scan is single-GPU (distributed sharding of sliding windows is not implemented)")
+        wss = sorted(set(int(w) for w in window_sizes))
+        step = self._check_steps(wss, step_size)
+        if not wss:
+            return {}
+        p = self._pack(data_dict)
+
+        def cfg_of(w):
+            return self._cfg(p, window_mode=L.WINDOW_BP, window=w, bg_mode=L.BG_PER_CHROM, fst=bool(fst), step=step)
+        eng = self._engine()
+        dev = eng.upload(p)
+        out = {}
+        try:
+            base = eng.plan(dev, cfg_of(wss[0]))
+            try:
+                plans = [base] + [base.attach(cfg_of(w)) for w in wss[1:]]
+                base.run()
+                base.check()
+                for w, pl in zip(wss, plans):
+                    pl.check()
+                    out[w] = post.sliding_scan(pl.read(), p, w, step, pl.read_fst() if fst else None)
+            finally:
+                base.close()
+        finally:
+            dev.close()
+        return out
+
     # ------------------------------------------------------------------ Fst (extension)
     def window_fst(self, data_dict, window_size=None, snp_window_size=None):
         """Hudson's Fst per window (not in the reference, whose published FST column is pixy's

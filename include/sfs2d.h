@@ -36,7 +36,8 @@ extern "C" {
 
 /* 2 (round 5-6): sfs2d_ctx_set_stream(ctx, NULL) selects the HIP null stream (1: the ctx's own),
  * sfs2d_ctx_use_own_stream / sfs2d_ctx_get_stream added, the sfs2d_dist_* entry points removed;
- * sfs2d_graph_* added (round 6, additive) */
+ * sfs2d_graph_* added (round 6, additive); sfs2d_plan_create_sliding / sfs2d_plan_attach_sliding added
+ * (additive: sfs2d_params keeps its layout, the step is an argument) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -244,6 +245,26 @@ int sfs2d_plan_run_phase(sfs2d_plan* plan, int phase, sfs2d_window* out_dev);
  * An attached plan is not run on its own (its run calls fail); read it with sfs2d_plan_read /
  * sfs2d_plan_fst_read after the base's run.  Destroying the base destroys its attached plans. */
 int sfs2d_plan_attach(sfs2d_plan* base, const sfs2d_params* params, sfs2d_plan** out);
+/* Sliding windows: a fixed-bp plan (params->window_mode == SFS2D_WINDOW_BP) whose windows of W =
+ * params->window bp advance by `step` bp instead of W: W % step == 0, 1 <= step <= W, W / step <= 64.  A
+ * chromosome with last position L has (L - 1) / step + 1 slots (one when L == 0); slot j holds the SNPs
+ * with j step + 1 <= pos <= j step + W (pos 0: slot 0 only).  The record's wid is j, begin / end its SNP
+ * range; a slot without SNPs is an SFS2D_W_EMPTY record.  Filters keep their meaning (SFS membership,
+ * not geometry); a per-chromosome background is the whole chromosome, counted once.  With step == W the
+ * plan is the ordinary one (records and Fst byte-equal).  The plan is used like any other: sfs2d_plan_run,
+ * _run_many, _run_streams, _read, _fst_read (every sliding plan with SFS2D_F_FST produces Fst), _check,
+ * timing, sfs2d_graph_*.  SFS2D_F_PREV_EXTRA (quirk Q9 of the disjoint window loop), SNP-count windows
+ * and a bad step are SFS2D_E_ARG, the reason in sfs2d_last_error.
+ * The reference has no sliding scan: its script scans the same data twice, at 20 kb and at 500 kb, and
+ * compares (twoDSFS_class.py:1923-1932), because a signal that straddles an edge of its disjoint
+ * windows is split between two of them; overlapping windows are what that double scan stands in for. */
+int sfs2d_plan_create_sliding(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* params, int64_t step,
+                              sfs2d_plan** out);
+/* The same as an attached plan (the rules of sfs2d_plan_attach; `base` is an ordinary or a sliding
+ * plan): several window sizes, sliding by one step, from ONE k_prep pass of the base -- the 20 kb +
+ * 500 kb pair of twoDSFS_class.py:1923-1932 as two sliding scans of one read of the SNP stream.  Fst of
+ * an attached sliding plan needs nothing of the base (no Fst flag, no dividing window). */
+int sfs2d_plan_attach_sliding(sfs2d_plan* base, const sfs2d_params* params, int64_t step, sfs2d_plan** out);
 /* launch geometry (threads per grid) of k_prep and of the scan kernel: matches the Grid_Size column
  * of rocprofv3 kernel traces, so profiles can be joined to a plan */
 int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* scan_threads);
