@@ -214,6 +214,16 @@ struct sfs2d_plan {
   bool fst_mask = true;           // Fst in the scan: the data set has SNPs with < 2 called alleles (k_scan_w FST 3 / 5)
   bool gate = false;              // Fst in the scan, folded, called counts within (n1, n2): k_scan_w's GATE variants
   int nfst = 0;                   // k_bg_slice's extra Fst workgroups
+  // bootstrap null (sfs2d_plan_null_run): the last call's task table and records
+  std::vector<NullTask> ntask_h;
+  NullTask* d_ntask = nullptr;
+  size_t ntask_cap = 0;
+  sfs2d_window* d_null = nullptr;        // plan-owned records (out_dev == NULL)
+  size_t null_cap = 0;
+  const sfs2d_window* null_last = nullptr;   // where the last call wrote (sfs2d_plan_null_read copies from it)
+  int64_t null_nrec = 0;
+  uint64_t null_tab_runs = ~0ull;        // fused / sliced plans: the run whose tables of EVERY chromosome are in
+                                         // d_tab / d_lp / d_head (their scans keep all but one chromosome's in LDS)
 };
 
 namespace {
@@ -258,6 +268,7 @@ void plan_free(sfs2d_plan* p) {
   hipFree(p->d_done); hipFree(p->d_bgval); hipFree(p->d_tab); hipFree(p->d_lp); hipFree(p->d_head);
   hipFree(p->d_bg1d); hipFree(p->d_leafsum); hipFree(p->d_leaves); hipFree(p->d_nodes); hipFree(p->d_slices);
   hipFree(p->d_out); hipFree(p->d_err); hipFree(p->d_bins); hipFree(p->d_fst_own); hipFree(p->d_fsum); hipFree(p->d_gscr);
+  hipFree(p->d_ntask); hipFree(p->d_null);
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->tev) if (e) hipEventDestroy(e);
 }
@@ -1879,6 +1890,142 @@ int sfs2d_plan_read(sfs2d_plan* pl, sfs2d_window* out_host, int64_t cap, int64_t
   const sfs2d_window* src = pl->last_out ? pl->last_out : pl->d_out;
   if (pl->nrec)
     HIPCHK(ctx, hipMemcpyAsync(out_host, src, sizeof(sfs2d_window) * pl->nrec, hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
+  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------ bootstrap null
+
+extern "C++" {
+namespace {
+
+// The tables k_null reads, complete for every chromosome.  Large-grid plans (k_bg_slice with its tail)
+// and supplied backgrounds (k_bg_finalize) leave them after every run.  The small-grid scans keep their
+// chromosome's finished table in LDS and store only the Q9 chromosome's, so:
+//   sliced: k_bg_slice left the table, the leaf sums, the 1D results and the run's inner sums -- its
+//           tail alone is missing (k_null_tail);
+//   fused:  the last run's replicas and inner sums are still in their parity buffer (the next scan
+//           clears them): k_bg_slice with its tail builds the tables from them.  It zeroes what it reads,
+//           which the next scan would do anyway, so it runs once per plan run (null_tab_runs).
+int null_tables(sfs2d_plan* pl) {
+  sfs2d_ctx* ctx = pl->ctx;
+  if (!pl->do_bg || !(pl->fused || pl->sliced) || pl->null_tab_runs == pl->runs) return 0;
+  const size_t lp = (size_t)((pl->runs - 1) & 1);   // parity of the last run
+  if (pl->fused) {
+    hipLaunchKernelGGL(k_bg_slice, dim3((unsigned)pl->slices.size() + 1, (unsigned)pl->nbg), dim3(KBLOCK), 0, CTX_STREAM(ctx),
+                       pl->K, pl->d_repl + lp * REPL * pl->K.nchrom * pl->K.nh, pl->d_bcount + lp * pl->K.nchrom, pl->d_tab,
+                       pl->d_lp, pl->d_head, pl->d_leafsum, pl->d_bg1d, pl->d_done, pl->d_slices, (int)pl->slices.size(),
+                       pl->d_leaves, pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels, 1, 0, pl->data->counts, scan_src(pl),
+                       pl->d_slots, reinterpret_cast<const double2*>(ctx->d_df + 2 * LNT), pl->d_fst, (uint32_t)pl->nslots);
+  } else {
+    hipLaunchKernelGGL(k_null_tail, dim3((unsigned)pl->nbg), dim3(KBLOCK), 0, CTX_STREAM(ctx), pl->K,
+                       pl->d_bcount + lp * pl->K.nchrom, pl->d_tab, pl->d_lp, pl->d_head, pl->d_leafsum, pl->d_bg1d,
+                       pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  pl->null_tab_runs = pl->runs;
+  return 0;
+}
+
+template <bool P16, bool CNT>
+int launch_null(sfs2d_plan* pl, uint32_t R, unsigned long long nrec, uint2 key, sfs2d_window* out) {
+  sfs2d_ctx* ctx = pl->ctx;
+  const KParams& K = pl->K;
+  // wavefronts per workgroup from the LDS a wave's histograms need: as many as fit 64 KB, at most 8
+  const size_t per = (size_t)null_wave_words(K.nb2, K.n1p, K.n2p, P16) * 4;
+  const int wpb = (int)std::max<size_t>(1, std::min<size_t>(NULL_MAX_WAVES, (64 * 1024) / per));
+  const size_t lds = per * wpb;
+  if (lds > 160 * 1024) return set_err(ctx, SFS2D_E_ARG, "2D grid too large for k_null's LDS histogram");
+  const void* f = (const void*)k_null<P16, CNT>;
+  if (lds > 64 * 1024) HIPCHK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_null<P16, CNT>, wpb * WAVE, lds) != hipSuccess || occ < 1) {
+    (void)hipGetLastError();
+    occ = 1;
+  }
+  // one resident set of workgroups striding over the records (a wave zeroes its histograms once)
+  const unsigned long long want = (nrec + wpb - 1) / wpb;
+  const unsigned grid = (unsigned)std::min<unsigned long long>(want, (unsigned long long)occ * ctx->ncu);
+  hipLaunchKernelGGL((k_null<P16, CNT>), dim3(grid), dim3(wpb * WAVE), lds, CTX_STREAM(ctx), K, scan_src(pl), pl->d_ntask, R,
+                     nrec, key, pl->d_tab, pl->d_head, pl->do_bg ? 1 : 0, ctx->d_lnx, out);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int sfs2d_plan_null_run(sfs2d_plan* pl, const sfs2d_null_params* np, const int64_t* tasks, int64_t ntasks,
+                        sfs2d_window* out_dev) {
+  if (!pl) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  const sfs2d_data* d = pl->data;
+  if (!np || ntasks < 0 || (ntasks > 0 && !tasks)) return set_err(ctx, SFS2D_E_ARG, "null argument");
+  if (pl->base) return set_err(ctx, SFS2D_E_ARG, "null run on an attached plan: use its base plan (same data, same tables)");
+  if (pl->runs == 0) return set_err(ctx, SFS2D_E_ARG, "null run before the plan's first run (no background tables yet)");
+  if (np->replicates < 1) return set_err(ctx, SFS2D_E_ARG, "null run: replicates must be >= 1");
+  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "null run: data set too large for 32-bit SNP indices");
+  pl->ntask_h.resize((size_t)ntasks);
+  uint32_t maxm = 0;
+  for (int64_t t = 0; t < ntasks; ++t) {
+    const int64_t pool = tasks[2 * t], m = tasks[2 * t + 1];
+    if (pool < -1 || pool >= d->nchrom) return set_err(ctx, SFS2D_E_ARG, "null run: pool " + std::to_string(pool) + " out of range");
+    if (pool == -1 && pl->do_bg)
+      return set_err(ctx, SFS2D_E_ARG, "null run: pool -1 (all SNPs) has no background on a per-chromosome plan");
+    const int64_t lo = pool < 0 ? 0 : d->chrom_off[pool], hi = pool < 0 ? d->n : d->chrom_off[pool + 1];
+    if (hi <= lo) return set_err(ctx, SFS2D_E_ARG, "null run: pool " + std::to_string(pool) + " is empty");
+    if (m < 1 || m > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "null run: m must be in [1, 2^32)");
+    NullTask k;
+    k.lo = (uint32_t)lo; k.n = (uint32_t)(hi - lo); k.m = (uint32_t)m; k.pool = (int32_t)pool;
+    pl->ntask_h[(size_t)t] = k;
+    maxm = std::max(maxm, k.m);
+  }
+  const unsigned long long nrec = (unsigned long long)ntasks * np->replicates;
+  if (nrec > (1ull << 26)) return set_err(ctx, SFS2D_E_CAP, "null run: more than 2^26 records in one call (split the tasks)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = CTX_STREAM(ctx);
+  if ((size_t)ntasks > pl->ntask_cap || (!out_dev && nrec > pl->null_cap)) {
+    HIPCHK(ctx, hipStreamSynchronize(st));   // an earlier call may still read what is replaced
+    if ((size_t)ntasks > pl->ntask_cap) {
+      hipFree(pl->d_ntask);
+      pl->ntask_cap = 0;
+      int rc = dalloc(ctx, &pl->d_ntask, (size_t)ntasks);
+      if (rc) return rc;
+      pl->ntask_cap = (size_t)ntasks;
+    }
+    if (!out_dev && nrec > pl->null_cap) {
+      hipFree(pl->d_null);
+      pl->null_cap = 0;
+      pl->null_last = nullptr;
+      pl->null_nrec = 0;
+      int rc = dalloc(ctx, &pl->d_null, (size_t)nrec);
+      if (rc) return rc;
+      pl->null_cap = (size_t)nrec;
+    }
+  }
+  sfs2d_window* out = out_dev ? out_dev : pl->d_null;
+  pl->null_last = out;
+  pl->null_nrec = (int64_t)nrec;
+  if (nrec == 0) return 0;
+  int rc = null_tables(pl);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(pl->d_ntask, pl->ntask_h.data(), sizeof(NullTask) * (size_t)ntasks, hipMemcpyHostToDevice, st));
+  const uint2 key = make_uint2((uint32_t)np->seed, (uint32_t)(np->seed >> 32));
+  // u16-packed 2D bins while no bin can hold 65536 draws
+  if (maxm <= 65535u)
+    return pl->cnt ? launch_null<true, true>(pl, np->replicates, nrec, key, out) : launch_null<true, false>(pl, np->replicates, nrec, key, out);
+  return pl->cnt ? launch_null<false, true>(pl, np->replicates, nrec, key, out) : launch_null<false, false>(pl, np->replicates, nrec, key, out);
+}
+
+int sfs2d_plan_null_read(sfs2d_plan* pl, sfs2d_window* out_host, int64_t cap, int64_t* nrec_out) {
+  if (!pl || !nrec_out) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  *nrec_out = pl->null_nrec;
+  if (cap < pl->null_nrec) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
+  if (pl->null_nrec && !out_host) return SFS2D_E_ARG;
+  if (pl->null_nrec)
+    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->null_last, sizeof(sfs2d_window) * (size_t)pl->null_nrec, hipMemcpyDeviceToHost,
+                               CTX_STREAM(ctx)));
   HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
   return 0;
 }

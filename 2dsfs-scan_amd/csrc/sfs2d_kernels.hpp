@@ -36,6 +36,7 @@
 //   k_scan_gw     large grids: k_scan_w's loop in one-wavefront workgroups, tables read from L2.
 //   k_scan_g      grids too large for k_scan_gw: one workgroup per window (exact evaluation).
 //   k_scan_extra  combined_scan's final-window helper (quirk Q9).
+//   k_null        the bootstrap null (sfs2d_null.hpp): one wavefront per replicate window of drawn SNPs.
 #pragma once
 
 #include <type_traits>
@@ -3572,5 +3573,8 @@ __global__ __launch_bounds__(256) void k_slots_synth(const unsigned long long* _
     slots[w] = b > a ? make_uint2((uint32_t)a + 1u, (uint32_t)b) : make_uint2(0u, 0u);
   }
 }
+
+// ------------------------------------------------------------------------------------------ bootstrap null
+#include "sfs2d_null.hpp"
 
 }  // namespace sfs2dk

@@ -42,7 +42,7 @@ EXPORTS = [
     "sfs2d_plan_stats", "sfs2d_plan_grids", "sfs2d_plan_scan_kernel", "sfs2d_plan_attach", "sfs2d_data_synth_sims",
     "sfs2d_data_read", "sfs2d_plan_run_streams", "sfs2d_ctx_use_own_stream", "sfs2d_bg_hist_dev", "sfs2d_plan_bg_rows_dev", "sfs2d_plan_bg_rows_set_dev",
     "sfs2d_ctx_get_stream", "sfs2d_plan_set_fst_out", "sfs2d_graph_create", "sfs2d_graph_launch", "sfs2d_graph_destroy",
-    "sfs2d_plan_create_sliding", "sfs2d_plan_attach_sliding",
+    "sfs2d_plan_create_sliding", "sfs2d_plan_attach_sliding", "sfs2d_plan_null_run", "sfs2d_plan_null_read",
 ]
 ABI_VERSION = 2   # SFS2D_ABI_VERSION of include/sfs2d.h
 
@@ -56,6 +56,10 @@ class Sfs2dError(RuntimeError):
 class SynthParams(C.Structure):   # sfs2d_synth_params
     _fields_ = [("seed", C.c_uint64), ("generation", C.c_uint32), ("n_replicates", C.c_uint32),
                 ("n_windows", C.c_uint32), ("window_bp", C.c_uint32), ("n1p", C.c_int32), ("n2p", C.c_int32)]
+
+
+class NullParams(C.Structure):   # sfs2d_null_params
+    _fields_ = [("seed", C.c_uint64), ("replicates", C.c_uint32)]
 
 
 class Params(C.Structure):
@@ -141,6 +145,8 @@ def lib():
     L.sfs2d_plan_attach.argtypes = [vp, C.POINTER(Params), C.POINTER(vp)]
     L.sfs2d_plan_create_sliding.argtypes = [vp, vp, C.POINTER(Params), i64, C.POINTER(vp)]
     L.sfs2d_plan_attach_sliding.argtypes = [vp, C.POINTER(Params), i64, C.POINTER(vp)]
+    L.sfs2d_plan_null_run.argtypes = [vp, C.POINTER(NullParams), vp, i64, vp]
+    L.sfs2d_plan_null_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sfs2d_data_synth_sims.argtypes = [vp, C.POINTER(SynthParams), vp, vp, i32, vp, i32, C.POINTER(vp)]
     L.sfs2d_data_read.argtypes = [vp, vp, vp, i64]
     L.sfs2d_ctx_use_own_stream.argtypes = [vp]

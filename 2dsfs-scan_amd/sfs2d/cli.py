@@ -18,6 +18,10 @@ window_end) the way ECBstats_plots.R:16-41 does (pixy chromosome ``NC_087088_1``
 
 ``--step BP`` makes every ``--window`` a sliding scan (windows advanced by BP, a divisor of each window;
 multi_sliding_scan): ``<prefix>_20kb_step5kb.csv`` with the same columns, clean None rules.
+
+``--null-replicates R [--null-seed S] [--null-sizes exact]`` appends six bootstrap p-value columns
+(``p_T2D`` ... ``p_T2D_diff``, after ``FST`` when present) to every output file: R windows of the same
+SNP count drawn from the window's chromosome per size class (scan_pvalues).
 """
 from __future__ import annotations
 
@@ -44,10 +48,14 @@ def read_pixy_fst(path):
     return out
 
 
-def write_csv(path, stats, chr_ids, fst=None, pixy=None):
-    """save_csv_stats (twoDSFS_class.py:1884-1907) + optional FST column."""
+P_COLS = ["p_T2D", "p_T1D_pop1", "p_T1D_pop2", "p_new_term_pop1", "p_new_term_pop2", "p_T2D_diff"]
+
+
+def write_csv(path, stats, chr_ids, fst=None, pixy=None, pvalues=False):
+    """save_csv_stats (twoDSFS_class.py:1884-1907) + optional FST column + optional p-value columns
+    (the rows' p_* keys, scan_pvalues)."""
     import twoDSFS_class as T
-    cols = list(T.col_names) + (["FST"] if (fst is not None or pixy is not None) else [])
+    cols = list(T.col_names) + (["FST"] if (fst is not None or pixy is not None) else []) + (P_COLS if pvalues else [])
     with open(path, "w", newline="") as fh:
         w = csv.DictWriter(fh, fieldnames=cols)
         w.writeheader()
@@ -62,6 +70,9 @@ def write_csv(path, stats, chr_ids, fst=None, pixy=None):
                 row["FST"] = fst.get(label)
             elif pixy is not None:
                 row["FST"] = pixy.get((chrom, s, e))
+            if pvalues:
+                for c in P_COLS:
+                    row[c] = r.get(c)
             w.writerow(row)
 
 
@@ -82,12 +93,21 @@ def main(argv=None):
     ap.add_argument("--chromosomes", default=None, help="accession<TAB>number map (chromosomes.txt)")
     ap.add_argument("--fst", action="store_true", help="append Hudson's Fst (this framework's estimator)")
     ap.add_argument("--pixy-fst", default=None, help="join pixy avg_wc_fst as the FST column")
+    ap.add_argument("--null-replicates", type=int, default=None, metavar="R",
+                    help="append bootstrap p-values: R resampled windows per chromosome and size class")
+    ap.add_argument("--null-seed", type=int, default=0, metavar="S")
+    ap.add_argument("--null-sizes", choices=["exact"], default=None,
+                    help="exact: a null for every distinct SNP count (default: a 9 %% geometric grid of sizes)")
     ap.add_argument("--out-prefix", default="stats")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="VCF parser threads (0 = all)")
     a = ap.parse_args(argv)
     if not a.window and not a.snp_window:
         a.window = [20000]
+    if a.null_replicates is not None and a.null_replicates < 1:
+        ap.error("--null-replicates must be >= 1")
+    null = a.null_replicates is not None
+    nkw = dict(replicates=a.null_replicates, seed=a.null_seed, sizes=a.null_sizes)
     if a.step is not None:
         if a.snp_window:
             ap.error("--step applies to fixed-bp windows: not with --snp-window")
@@ -114,30 +134,36 @@ def main(argv=None):
     outs = []
     t = time.perf_counter()
     if a.step is not None:   # sliding windows: every size from one upload and one k_prep pass
-        res = obj.multi_sliding_scan(packed, a.window, a.step, fst=a.fst)
+        if null:
+            res = obj.scan_pvalues(packed, a.window, step_size=a.step, fst=a.fst, **nkw)
+        else:
+            res = obj.multi_sliding_scan(packed, a.window, a.step, fst=a.fst)
         print(f"multi_sliding_scan ({len(a.window)} window sizes, step {a.step}): {time.perf_counter() - t:.2f} s",
               file=sys.stderr)
         for ws in a.window:
             path = f"{a.out_prefix}_{_fmt_kb(ws)}_step{_fmt_kb(a.step)}.csv"
             rows = res[ws]
-            write_csv(path, rows, chr_ids, {k: r["FST"] for k, r in rows.items()} if a.fst else None, pixy)
+            write_csv(path, rows, chr_ids, {k: r["FST"] for k, r in rows.items()} if a.fst else None, pixy, null)
             outs.append(path)
             print(f"sliding_scan {ws} bp / {a.step} bp: {len(rows)} windows -> {path}", file=sys.stderr)
         return outs
     # every window size from one k_prep pass over the resident stream (sfs2d_plan_attach)
-    res = obj.multi_scan(packed, a.window, a.snp_window, fst=a.fst)
+    if null:
+        res = obj.scan_pvalues(packed, a.window, a.snp_window, fst=a.fst, **nkw)
+    else:
+        res = obj.multi_scan(packed, a.window, a.snp_window, fst=a.fst)
     print(f"multi_scan ({len(a.window)} bp + {len(a.snp_window)} SNP-count window sizes): "
           f"{time.perf_counter() - t:.2f} s", file=sys.stderr)
     for ws in a.window:
         path = f"{a.out_prefix}_{_fmt_kb(ws)}.csv"
-        write_csv(path, res[ws], chr_ids, res["fst"][ws] if a.fst else None, pixy)
+        write_csv(path, res[ws], chr_ids, res["fst"][ws] if a.fst else None, pixy, null)
         outs.append(path)
         print(f"combined_scan {ws} bp: {len(res[ws])} windows -> {path}", file=sys.stderr)
     for S in a.snp_window:
         stats = res[f"{S}snps"]
         fst = obj.window_fst(packed, snp_window_size=S) if a.fst else None
         path = f"{a.out_prefix}_{S}snps.csv"
-        write_csv(path, stats, chr_ids, fst, pixy)
+        write_csv(path, stats, chr_ids, fst, pixy, null)
         outs.append(path)
         print(f"scan_perChr_bySNPs {S} SNPs: {len(stats)} windows -> {path}", file=sys.stderr)
     return outs

@@ -286,6 +286,46 @@ class Plan:
         self.eng.check(self.eng.lib.sfs2d_plan_read(self.h, L.ptr(out), self.nrec, C.byref(n)))
         return out
 
+    def null_run(self, tasks, replicates: int, seed: int, out_dev_ptr: Optional[int] = None):
+        """The bootstrap null of this plan's last run (sfs2d_plan_null_run): ``tasks`` = (pool, m) pairs
+        (pool: a chromosome index, or -1 = all SNPs on a supplied-background plan), ``replicates`` windows
+        of m SNPs drawn with replacement from the pool per task, evaluated against the pool's background.
+        Record t * replicates + r is replicate r of task t.  The tasks are split over calls of at most
+        2**22 records; with ``out_dev_ptr`` (a device buffer of len(tasks) * replicates records) nothing
+        is copied to the host, else ``null_read`` returns the records."""
+        from .null import MAX_CALL_RECORDS
+        tk = np.ascontiguousarray(np.asarray(list(tasks), np.int64).reshape(-1, 2))
+        R = int(replicates)
+        if R < 0 or R > 0xFFFFFFFF:
+            raise ValueError("replicates out of range")
+        npar = L.NullParams(seed=int(seed) & 0xFFFFFFFFFFFFFFFF, replicates=R)
+        per = max(1, MAX_CALL_RECORDS // max(1, R))   # tasks per call
+        self._null_parts = []
+        nt = max(1, len(tk))
+        for a in range(0, nt, per):
+            part = np.ascontiguousarray(tk[a:a + per])
+            out = C.c_void_p(out_dev_ptr + a * R * L.WINDOW_DTYPE.itemsize) if out_dev_ptr else None
+            self.eng.check(self.eng.lib.sfs2d_plan_null_run(self.h, C.byref(npar), L.ptr(part), len(part), out))
+            self._null_call_n = len(part) * R
+            if not out_dev_ptr and nt > per:   # the plan-owned buffer holds one call's records
+                self._null_parts.append(self._null_read_call())
+        self._null_dev = bool(out_dev_ptr)
+
+    def _null_read_call(self) -> np.ndarray:
+        n = C.c_int64()
+        out = np.zeros(self._null_call_n, dtype=L.WINDOW_DTYPE)   # the records of the last call
+        self.eng.check(self.eng.lib.sfs2d_plan_null_read(self.h, L.ptr(out) if len(out) else None, len(out), C.byref(n)))
+        return out
+
+    def null_read(self) -> np.ndarray:
+        """The records of the last ``null_run`` (numpy structured array, WINDOW_DTYPE; synchronises)."""
+        if getattr(self, "_null_dev", False):
+            raise ValueError("the last null_run wrote to the caller's device buffer")
+        parts = getattr(self, "_null_parts", None)
+        if parts is None:
+            raise ValueError("null_read before null_run")
+        return np.concatenate(parts) if parts else self._null_read_call()
+
     def bg_buffer(self):
         p = C.c_void_p()
         nb = C.c_int64()

@@ -206,6 +206,32 @@ def bysnp_scan(recs, packed, S, with_diff, final_warning):
     return res
 
 
+def record_labels(recs, packed, kind, w, step=None):
+    """The result-dict label of every record of a plan (None: a record that is no window of its own --
+    empty slot, Q9 helper, an S-SNP window without 2D SFS entries), as the drivers above make them:
+    kind "bp" (combined_scan / fixed_bg_scan; ``step``: sliding_scan) or "snps" (bysnp_scan).  A driver may
+    still leave a labelled window out of its dict (combined_scan's final block)."""
+    names = packed.chrom_names
+    out = [None] * len(recs)
+    if kind == "bp":
+        adv = w if step is None else step
+        for i, r in enumerate(recs):
+            if r["flags"] & (L.W_EMPTY | L.W_EXTRA):
+                continue
+            s = 1 + int(r["wid"]) * adv
+            out[i] = f"{names[int(r['chrom'])]} {s}-{s + w - 1}"
+        return out
+    start = {}
+    for i, r in enumerate(recs):
+        c = int(r["chrom"])
+        st = start.get(c, int(packed.pos[int(packed.chrom_off[c])]))
+        endp = int(packed.pos[int(r["end"]) - 1])
+        if r["n2_all"] != 0:
+            out[i] = f"{names[c]} {st}-{endp}"
+        start[c] = endp + 1
+    return out
+
+
 def window_fst_labels(recs, fst, packed, w, bp):
     """{window label: Fst or None} in scan order; labels as combined_scan (bp windows: wid) or the
     bySNPs drivers (first SNP position - last SNP position of each complete S-SNP window) make them."""

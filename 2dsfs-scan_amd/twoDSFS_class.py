@@ -277,6 +277,11 @@ class LikelihoodInference_jointSFS:
         fixed-bp scan is the base plan, the others are attached to it (sfs2d_plan_attach).
         Returns {ws: combined_scan result, "<S>snps": scan_perChr_bySNPs result}, plus
         {"fst": {ws: window_fst result}} when ``fst`` (fixed-bp windows only)."""
+        return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst)
+
+    def _multi_scan(self, data_dict, window_sizes, snp_window_sizes, fst, after_run=None):
+        """multi_scan; ``after_run(p, base plan, [(recs, record labels, rows)])`` is called while the
+        plans are alive (scan_pvalues adds its columns there)."""
         p = self._pack(data_dict)
         bps = sorted(set(int(w) for w in window_sizes))
         snps = [int(x) for x in dict.fromkeys(snp_window_sizes)]
@@ -308,6 +313,7 @@ class LikelihoodInference_jointSFS:
                         plans.append(base.attach(c))
                 base.run()
                 base.check()
+                items = []
                 for (kind, w), pl in zip(specs, plans):
                     pl.check()
                     recs = pl.read()
@@ -317,6 +323,10 @@ class LikelihoodInference_jointSFS:
                             out.setdefault("fst", {})[w] = post.window_fst_labels(recs, pl.read_fst(), p, w, True)
                     else:
                         out[f"{w}snps"] = post.bysnp_scan(recs, p, w, with_diff=True, final_warning=False)
+                    if after_run is not None:
+                        items.append((recs, post.record_labels(recs, p, kind, w), out[w if kind == "bp" else f"{w}snps"]))
+                if after_run is not None:
+                    after_run(p, base, items)
             finally:
                 base.close()
         finally:
@@ -383,6 +393,10 @@ class LikelihoodInference_jointSFS:
         ONE upload and one k_prep pass: the smallest window is a sliding plan of its own, the others are
         attached to it (sfs2d_plan_attach_sliding).  Returns {window_size: sliding_scan rows}.  A window the
         step does not divide raises ValueError before any GPU work."""
+        return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst)
+
+    def _multi_sliding_scan(self, data_dict, window_sizes, step_size, fst, after_run=None):
+        """multi_sliding_scan, with ``after_run`` as in _multi_scan."""
         if self.distributed:
             raise NotImplementedError("multi_sliding_scan is single-GPU (distributed sharding of sliding windows is not implemented)")
         wss = sorted(set(int(w) for w in window_sizes))
@@ -402,14 +416,129 @@ class LikelihoodInference_jointSFS:
                 plans = [base] + [base.attach(cfg_of(w)) for w in wss[1:]]
                 base.run()
                 base.check()
+                items = []
                 for w, pl in zip(wss, plans):
                     pl.check()
-                    out[w] = post.sliding_scan(pl.read(), p, w, step, pl.read_fst() if fst else None)
+                    recs = pl.read()
+                    out[w] = post.sliding_scan(recs, p, w, step, pl.read_fst() if fst else None)
+                    if after_run is not None:
+                        items.append((recs, post.record_labels(recs, p, "bp", w, step), out[w]))
+                if after_run is not None:
+                    after_run(p, base, items)
             finally:
                 base.close()
         finally:
             dev.close()
         return out
+
+    # ------------------------------------------------------------------ bootstrap null (extension)
+    def _null_columns(self, p, base, items, replicates, seed, sizes, pool=None):
+        """Add the six p_* keys to every row of ``items`` ([(records, record labels, rows)] of plans that
+        share ``base``'s data and tables): one null run on ``base`` over the union of the (pool, size class)
+        pairs of all windows, the exceedance counts taken on the device (sfs2d.null.pvalues_device).
+        pool: the background chromosome of every window (None: each window's own chromosome)."""
+        import torch
+        from sfs2d import null as N
+        sel = []
+        for recs, labels, rows in items:
+            idx = np.array([i for i, lb in enumerate(labels) if lb is not None and lb in rows], np.int64)
+            sel.append((recs[idx], [labels[i] for i in idx], rows))
+        obs = np.concatenate([s[0] for s in sel]) if sel else np.zeros(0, L.WINDOW_DTYPE)
+        if len(obs) == 0:
+            return
+        m = obs["end"].astype(np.int64) - obs["begin"].astype(np.int64)
+        classes = N.size_classes(m, sizes)
+        pools = obs["chrom"].astype(np.int64) if pool is None else np.full(len(obs), int(pool), np.int64)
+        tasks = sorted(set(zip(pools.tolist(), classes.tolist())))
+        R = int(replicates)
+        eng = base.eng
+        buf = torch.empty(len(tasks) * R * L.WINDOW_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{self.device}")
+        torch.cuda.synchronize(buf.device)   # (the engine's stream is ordered against nothing of torch's)
+        base.null_run(tasks, R, seed, out_dev_ptr=buf.data_ptr())
+        h = eng.stream_handle()
+        if h:
+            torch.cuda.ExternalStream(h, device=buf.device).synchronize()
+        else:
+            torch.cuda.synchronize(buf.device)
+        pv = N.pvalues_device(obs, classes, buf, tasks, R, pools)
+        k = 0
+        for recs, labels, rows in sel:
+            for lb in labels:
+                for key in N.P_KEYS:
+                    v = pv[key][k]
+                    rows[lb][key] = None if np.isnan(v) else float(v)
+                k += 1
+
+    def scan_pvalues(self, data_dict, window_sizes=(), snp_window_sizes=(), step_size=None,
+                     background_chromosome=None, replicates=999, seed=0, sizes=None, fst=False):
+        """The scans of ``multi_scan`` (``step_size`` given: ``multi_sliding_scan``) with a bootstrap p-value
+        beside every statistic: each row additionally holds p_T2D, p_T1D_pop1, p_T1D_pop2, p_new_term_pop1,
+        p_new_term_pop2 and p_T2D_diff -- the share of ``replicates`` windows of the same number of SNPs
+        (rounded up to a size class, sfs2d.null.size_classes; ``sizes``: None, "exact" or a list) drawn with
+        replacement from the window's background chromosome whose statistic is at least the window's
+        (definition, what the null does not model).  The p-values of the derived
+        terms are formed from the window's own three T's (None when one is None), not from
+        combined_scan's carried values.  One null run per call serves every window size.
+        ``background_chromosome``: one window size, scanned as scan_chooseChr (or scan_chooseChr_bySNPs for a
+        SNP-count size, sliding_scan with ``step_size``) does; that chromosome is every window's pool; the
+        result is {size: rows}.  Not in the reference (it thresholds by SNP-count quantile and top 1 % in R,
+        ECBstats_plots.R:45-50, 147-219)."""
+        if self.distributed:
+            raise NotImplementedError("scan_pvalues is single-GPU (distributed sharding of the null is not implemented)")
+        if int(replicates) < 1:
+            raise ValueError(f"replicates must be >= 1, got {replicates}")
+        if sizes is not None and sizes != "exact":
+            sizes = sorted(int(x) for x in sizes)
+
+        def hook(pool=None):
+            return lambda p, base, items: self._null_columns(p, base, items, replicates, seed, sizes, pool)
+        if background_chromosome is None:
+            if step_size is None:
+                return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, hook())
+            if len(tuple(snp_window_sizes)):
+                raise ValueError("step_size applies to fixed-bp windows: not with snp_window_sizes")
+            return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, hook())
+        # one chromosome as every window's background (and pool)
+        bps, snps = [int(w) for w in window_sizes], [int(w) for w in snp_window_sizes]
+        if len(bps) + len(snps) != 1:
+            raise ValueError("background_chromosome takes exactly one window size")
+        if step_size is not None and snps:
+            raise ValueError("step_size applies to fixed-bp windows: not with snp_window_sizes")
+        if fst and step_size is None:
+            raise ValueError("fst with background_chromosome needs step_size (scan_chooseChr has no Fst)")
+        p = self._pack(data_dict)
+        if background_chromosome not in p.chrom_names:
+            raise ValueError(f"Background chromosome {background_chromosome} not found in the data.")
+        bgc = p.chrom_names.index(background_chromosome)
+        bg = self._bg_arrays(p, bgc)
+        step = None if step_size is None else self._check_steps(bps, step_size)
+        if snps:   # scan_chooseChr_bySNPs: the normalised background
+            bg = tuple(np.array(self._normalize_values(np.asarray(b).ravel().tolist())) for b in bg)
+        w = (bps or snps)[0]
+        cfg = self._cfg(p, window_mode=L.WINDOW_SNPS if snps else L.WINDOW_BP, window=w, bg_mode=L.BG_SUPPLIED,
+                        step=step, fst=bool(fst))
+        eng = self._engine()
+        dev = eng.upload(p)
+        try:
+            pl = eng.plan(dev, cfg)
+            try:
+                pl.set_background(*bg)
+                pl.run()
+                pl.check()
+                recs = pl.read()
+                if snps:
+                    rows = post.bysnp_scan(recs, p, w, with_diff=False, final_warning=True)
+                elif step is not None:
+                    rows = post.sliding_scan(recs, p, w, step, pl.read_fst() if fst else None)
+                else:
+                    rows = post.fixed_bg_scan(recs, p, w, post.num_slots(recs))
+                labels = post.record_labels(recs, p, "snps" if snps else "bp", w, step)
+                self._null_columns(p, pl, [(recs, labels, rows)], replicates, seed, sizes, pool=bgc)
+            finally:
+                pl.close()
+        finally:
+            dev.close()
+        return {(f"{w}snps" if snps else w): rows}
 
     # ------------------------------------------------------------------ Fst (extension)
     def window_fst(self, data_dict, window_size=None, snp_window_size=None):

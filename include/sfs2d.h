@@ -37,7 +37,8 @@ extern "C" {
 /* 2 (round 5-6): sfs2d_ctx_set_stream(ctx, NULL) selects the HIP null stream (1: the ctx's own),
  * sfs2d_ctx_use_own_stream / sfs2d_ctx_get_stream added, the sfs2d_dist_* entry points removed;
  * sfs2d_graph_* added (round 6, additive); sfs2d_plan_create_sliding / sfs2d_plan_attach_sliding added
- * (additive: sfs2d_params keeps its layout, the step is an argument) */
+ * (additive: sfs2d_params keeps its layout, the step is an argument); sfs2d_plan_null_run / _null_read added
+ * (additive) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -265,6 +266,30 @@ int sfs2d_plan_create_sliding(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2
  * 500 kb pair of twoDSFS_class.py:1923-1932 as two sliding scans of one read of the SNP stream.  Fst of
  * an attached sliding plan needs nothing of the base (no Fst flag, no dividing window). */
 int sfs2d_plan_attach_sliding(sfs2d_plan* base, const sfs2d_params* params, int64_t step, sfs2d_plan** out);
+/* Bootstrap null of T2D / T1D: how large is a window's T under "this window is a random
+ * sample of its background"?  A task is a pair (pool, m): pool = a chromosome index c, meaning the SNPs
+ * [chrom_off[c], chrom_off[c+1]) of the plan's data set, or -1, all of them (every SNP of the range, whatever
+ * the filters: a drawn SNP carries its own classification and still counts toward m, as end - begin does for
+ * a real window); m >= 1 SNPs are drawn from it with replacement, `replicates` times.  Draw j of replicate r:
+ * c = philox4x32(counter (j >> 1, r, m, pool + 1), key (seed & 0xffffffff, seed >> 32)); x64 = c.x | c.y << 32
+ * for even j, c.z | c.w << 32 for odd j; SNP index = lo + mulhi64(x64, n) (lo, n: the pool's first index and
+ * size) -- a function of (seed, pool, m, r, j) alone, whatever the order or split of the tasks.  Record
+ * t * replicates + r is replicate r of task t, evaluated as the scan's exact path evaluates a window, against
+ * the background the plan uses for the pool (SFS2D_BG_PER_CHROM: table `pool`, pool -1 refused;
+ * SFS2D_BG_SUPPLIED: the supplied table, any pool): chrom = pool (0xffffffff for -1), wid = r, begin = 0,
+ * end = m, the counts, SFS2D_W_BG*_ZERO flags and T's as the scan writes them.  The drawn windows are never
+ * stored.  tasks: ntasks (pool, m) pairs on the host; out_dev: ntasks * replicates records on the device
+ * (NULL = plan-owned, read with sfs2d_plan_null_read).  Enqueued on the ctx stream after the plan's last run,
+ * which it leaves as it found it (the next run's records and Fst are byte-equal).  SFS2D_E_ARG, with the
+ * reason in sfs2d_last_error: a plan that has not run, an attached plan (use its base: same data, same
+ * tables), a pool out of range, pool -1 on a per-chromosome plan, an empty pool, m < 1, replicates < 1;
+ * SFS2D_E_CAP: more than 2^26 records in one call, or sfs2d_plan_null_read's cap below the record count.
+ * The reference has no null: its R script thresholds windows by SNP-count quantile and top 1 %
+ * (ECBstats_plots.R:45-50, 147-219). */
+typedef struct { uint64_t seed; uint32_t replicates; } sfs2d_null_params;
+int sfs2d_plan_null_run(sfs2d_plan* plan, const sfs2d_null_params* np, const int64_t* tasks, int64_t ntasks,
+                        sfs2d_window* out_dev);
+int sfs2d_plan_null_read(sfs2d_plan* plan, sfs2d_window* out_host, int64_t cap, int64_t* nrec_out);
 /* launch geometry (threads per grid) of k_prep and of the scan kernel: matches the Grid_Size column
  * of rocprofv3 kernel traces, so profiles can be joined to a plan */
 int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* scan_threads);
