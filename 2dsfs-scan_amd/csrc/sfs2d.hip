@@ -222,6 +222,10 @@ struct sfs2d_plan {
   size_t null_cap = 0;
   const sfs2d_window* null_last = nullptr;   // where the last call wrote (sfs2d_plan_null_read copies from it)
   int64_t null_nrec = 0;
+  // template arguments of the scan kernel the last run launched (sfs2d_plan_scan_variant), written by the
+  // launch_scan_* templates themselves: {P16, FUSED, FST, CNT, GATE, TRI}, -1 where the kernel has none
+  int variant[6] = {-1, -1, -1, -1, -1, -1};
+  bool variant_set = false;
   uint64_t null_tab_runs = ~0ull;        // fused / sliced plans: the run whose tables of EVERY chromosome are in
                                          // d_tab / d_lp / d_head (their scans keep all but one chromosome's in LDS)
 };
@@ -283,8 +287,15 @@ int repl_par(const sfs2d_plan* pl) { return pl->fused ? plan_par(pl) : 0; }
 // what the scan kernels stream per SNP: the bins k_prep wrote, or (counts plans) the counts themselves
 const uint32_t* scan_src(const sfs2d_plan* pl) { return pl->cnt ? pl->data->counts : pl->d_bins; }
 
+void set_variant(sfs2d_plan* pl, int p16, int fused, int fst, int cnt, int gate, int tri) {
+  const int v[6] = {p16, fused, fst, cnt, gate, tri};
+  std::copy(v, v + 6, pl->variant);
+  pl->variant_set = true;
+}
+
 template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false>
 void launch_scan_w(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
+  set_variant(pl, P16, FUSED, FST, CNT, GATE, -1);
   hipExtLaunchKernelGGL((k_scan_w<P16, FUSED, FST, CNT, GATE>), dim3((unsigned)pl->chunks.size()), dim3(SBLOCK), pl->scan_lds,
                      CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_lp, pl->d_head,
                      per_chrom, pl->ctx->d_lnx, pl->ctx->d_df, out, pl->d_err, bp, pl->d_repl, pl->d_bcount,
@@ -295,6 +306,7 @@ void launch_scan_w(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
 
 template <bool P16, bool FST, bool CNT>
 void launch_scan_g(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
+  set_variant(pl, P16, -1, FST, CNT, -1, -1);
   hipExtLaunchKernelGGL((k_scan_g<P16, FST, CNT>), dim3((unsigned)pl->chunks.size()), dim3(BLOCK), pl->scan_lds,
                      CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_head, per_chrom,
                      pl->ctx->d_lnx, out, bp, pl->d_fsum, pl->d_fst);
@@ -302,6 +314,7 @@ void launch_scan_g(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
 
 template <bool P16, bool FST, bool CNT, bool TRI = false>
 void launch_scan_gw(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
+  set_variant(pl, P16, -1, FST, CNT, -1, TRI);
   hipExtLaunchKernelGGL((k_scan_gw<P16, FST, CNT, TRI>), dim3((unsigned)pl->chunks.size()), dim3(WAVE), pl->scan_lds,
                      CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_lp, pl->d_head,
                      per_chrom, pl->ctx->d_lnx, pl->ctx->d_df, out, pl->d_err, bp, pl->d_repl, pl->d_bcount,
@@ -1517,6 +1530,15 @@ const char* sfs2d_plan_scan_kernel(const sfs2d_plan* pl) {
   if (!pl) return nullptr;
   if (pl->gw) return "k_scan_gw";
   return pl->G == WAVE ? "k_scan_w" : "k_scan_g";
+}
+
+int sfs2d_plan_scan_variant(const sfs2d_plan* pl, int* p16, int* fused, int* fst, int* cnt, int* gate, int* tri) {
+  if (!pl) return SFS2D_E_ARG;
+  if (!pl->variant_set) return set_err(pl->ctx, SFS2D_E_ARG, "sfs2d_plan_scan_variant: the plan has launched no scan kernel yet");
+  int* const o[6] = {p16, fused, fst, cnt, gate, tri};
+  for (int i = 0; i < 6; ++i)
+    if (o[i]) *o[i] = pl->variant[i];
+  return 0;
 }
 
 int sfs2d_plan_set_timing(sfs2d_plan* pl, int max_runs) { return sfs2d_plan_set_timing_sampled(pl, max_runs, 1); }

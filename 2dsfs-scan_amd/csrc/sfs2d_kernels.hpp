@@ -1212,7 +1212,9 @@ __device__ __forceinline__ void fst_windows(const KParams& P, const uint32_t* __
     double tn, ta, tb;
     wave_sum_dpp_halves(sn, sd, tn, ta, tb);
     const double td = ta + tb;
-    if (lane == 0) fst_out[s] = td != 0.0 ? tn / td : __builtin_nan("");
+    // (a sum below 2^-10 is rounding alone: a member fixed for the alternative allele in both populations has
+    // den = 0 but p = a * (1 / n) not exactly 1; any other member adds >= 1 / 510 -- as k_scan_w's flush)
+    if (lane == 0) fst_out[s] = td >= 0x1p-10 ? tn / td : __builtin_nan("");
   }
 }
 
@@ -1777,10 +1779,12 @@ struct Win {
   bool has;
 };
 
-// F(x) = x ln x from the LDS table (N entries), the global ln table beyond it
+// F(x) = x ln x from the LDS table (N entries), the global ln table beyond it.  (x >= LNX_N: only in a window
+// of >= 65,535 SNPs, whose fast-path value the flush drops for eval_exact's; the clamp keeps that read inside
+// the table)
 template <int N = LNT>
 __device__ __forceinline__ double xlnx(uint32_t x, const double* Ft, const double* lnx) {
-  return x < (uint32_t)N ? Ft[x] : (double)x * lnx[x];
+  return x < (uint32_t)N ? Ft[x] : (double)x * lnx[min(x, (uint32_t)LNX_N - 1u)];
 }
 
 // The fused prologue of k_scan_w (kept out of line: it runs once per workgroup and its registers
@@ -2806,14 +2810,19 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       if (FSTIN) {   // the window's own sums
         const double fx = __longlong_as_double((long long)sh_bf[wv][0][jl]);
         const double fy = __longlong_as_double((long long)sh_bf[wv][FST ? 1 : 0][jl]);
-        fst_out[Bs] = fy != 0.0 ? fx / fy : __builtin_nan("");
+        // den of one SNP is 0 (p1 = p2 = 0 or 1) or >= 1 / 510 (u8 counts), but p = a * (1 / n) is not exactly 1
+        // for every a = n: a window of SNPs fixed for the alternative allele with missing calls sums to
+        // ~1e-16 instead of 0.  Below 2^-10 the sum is that rounding alone (it stays under 2^-14 for windows
+        // of up to 2^22 SNPs): no SNP qualifies, NaN as for an exact 0
+        fst_out[Bs] = fy >= 0x1p-10 ? fx / fy : __builtin_nan("");
       } else if (FST) {   // k_prep's fixed-point sums of the slot (read in the window), cleared for the next run
         const long long fx = (long long)sh_bf[wv][0][jl], fy = (long long)sh_bf[wv][FST ? 1 : 0][jl];
         fst_out[Bs] = fy != 0 ? (double)fx / (double)fy : __builtin_nan("");
         reinterpret_cast<ulonglong2*>(fsum)[Bs] = make_ulonglong2(0ull, 0ull);
       }
     }
-      if (mine && mode_bp && !FSTIN) {
+      if (mine && mode_bp && !FSTIN && !exact) {
+        // (not a window re-evaluated below: a saturated size takes its end from this record)
         // the slot is cleared after its read although k_prep rewrites the table every run: without this
         // store the overlapped Fst-free config-3 pass measured 0.194-0.197 vs 0.162-0.174 ms per pass
         // (profiles/r05r_scan_slot_store_ab.txt).  With Fst in the scan it is left out: no difference in

@@ -347,6 +347,14 @@ class Plan:
         """Name of the scan kernel this plan launches (the prefix of its rocprofv3 kernel name)."""
         return self.eng.lib.sfs2d_plan_scan_kernel(self.h).decode()
 
+    def scan_variant(self) -> dict:
+        """Template arguments of the scan kernel this plan's last run launched (sfs2d_plan_scan_variant):
+        {"p16", "fused", "fst", "cnt", "gate", "tri"}, -1 where the kernel has no such argument; raises
+        before the plan has run."""
+        v = [C.c_int() for _ in range(6)]
+        self.eng.check(self.eng.lib.sfs2d_plan_scan_variant(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("p16", "fused", "fst", "cnt", "gate", "tri"), (x.value for x in v)))
+
     def stats(self) -> int:
         v = C.c_uint32()
         self.eng.check(self.eng.lib.sfs2d_plan_stats(self.h, C.byref(v)))

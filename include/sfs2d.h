@@ -296,6 +296,11 @@ int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* sca
 /* name of the scan kernel the plan launches ("k_scan_w", "k_scan_gw", "k_scan_g"; the
  * prefix of its rocprofv3 kernel name), NULL for a null plan */
 const char* sfs2d_plan_scan_kernel(const sfs2d_plan* plan);
+/* template arguments of the scan kernel the plan's last run launched; -1 where the kernel has no such argument
+ * (k_scan_w: p16, fused, fst 0..3, cnt, gate; k_scan_gw: p16, fst, cnt, tri; k_scan_g: p16, fst, cnt).  p16 == 0:
+ * 32-bit 2D bins in LDS (a window may hold >= 65,536 SNPs).  An attached plan records at its own launch inside
+ * its base's run.  SFS2D_E_ARG before any run (or when no run launched a scan kernel); NULL outputs are skipped */
+int sfs2d_plan_scan_variant(const sfs2d_plan* plan, int* p16, int* fused, int* fst, int* cnt, int* gate, int* tri);
 /* cumulative number of windows re-evaluated on the exact path (|T| ~ 0: proportionality test) */
 int sfs2d_plan_stats(sfs2d_plan* plan, uint32_t* exact_windows);
 /* last run's error word (0 = ok, else SFS2D_E_KEY / SFS2D_E_GRID, or SFS2D_E_ARG for summed background

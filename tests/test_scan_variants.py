@@ -7,6 +7,7 @@ import pytest
 
 import golden_util as gu
 from oracle import sfs_oracle as O
+from wide_util import check_records as _check
 
 pytestmark = pytest.mark.gpu
 
@@ -32,29 +33,6 @@ def _oracle(key, p, fold=True):
         fst = [O.window_fst(p, np.arange(w[2], w[3]), ocfg) for w in wins]
         _REF[key] = (wins, recs, fst)
     return _REF[key]
-
-
-def _check(recs, fst, ref):
-    from sfs2d import _lib as L
-    wins, orec, ofst = ref
-    live = (recs["flags"] & L.W_EMPTY) == 0
-    body = recs[live]
-    assert len(body) == len(wins), (len(body), len(wins))
-    assert np.all(np.isnan(fst[: len(live)][~live[: len(fst)]]))
-    fl = fst[: len(live)][live[: len(fst)]]
-    assert len(fl) == len(wins)
-    for i, (w, r, o, f) in enumerate(zip(wins, body, orec, ofst)):
-        assert (int(r["chrom"]), int(r["begin"]), int(r["end"])) == (w[0], w[2], w[3]), (i, w)
-        for a, b in (("snp_count", "snp_count"), ("n2", "N2"), ("n2_all", "N2_all"), ("n1a", "N1a"), ("n1b", "N1b")):
-            assert int(r[a]) == o[b], (i, a, int(r[a]), o[b])
-        for a, b in (("t2d", "T2D"), ("t1d_p1", "T1D_p1"), ("t1d_p2", "T1D_p2")):
-            v = float(r[a])
-            if o[b] is None:   # an empty spectrum: the record holds 0 or NaN (the host post-pass reports None)
-                assert v == 0.0 or np.isnan(v), (i, a, v)
-            else:
-                assert gu.close(v, o[b]), (i, a, v, o[b])
-        g = float(fl[i])
-        assert (np.isnan(g) if f is None else abs(g - f) <= 1e-12 + 1e-10 * abs(f)), (i, "fst", g, f)
 
 
 def _scan(p, **kw):
