@@ -1713,6 +1713,47 @@ __device__ __forceinline__ WinOut eval_exact(const KParams& P, const uint32_t* _
   const double N2 = (double)o.n2, N1a = (double)o.n1a, N1b = (double)o.n1b;
   double s2 = 0.0, sa = 0.0, sb = 0.0;
   bool q2 = true, qa = true, qb = true;   // x_k/N == p_k bitwise on every touched bin
+  [[maybe_unused]] auto term = [&](uint32_t x, int k, double N, double B, double& s, bool& q) {
+    const PL t = T.at(k);
+    s += (double)x * (lnx_of(lnx, x) - t.lp);
+    q &= prop_ok(x, N, t.v, B, floatv);
+  };
+  if constexpr (G > WAVE) {
+    // A bin's term is summed by the lane whose take finds the count.  Within one wavefront that lane is fixed
+    // by the data; the wavefronts of a workgroup raced for it, which changed the lane sums' rounding from run to
+    // run.  So the SNPs go in chunks of U per lane: the words are loaded by all wavefronts at once, the takes (LDS
+    // only) are done wavefront after wavefront, and the table reads and sums again by all at once: T is a
+    // function of the window and the table alone, bitwise.
+    constexpr int U = 4;
+    const int wv = (int)(threadIdx.x / WAVE);
+    for (unsigned long long base = b; base < e; base += (unsigned long long)(G * U)) {
+      uint32_t k2[U], g1[U], g2[U], x2[U], xa[U], xb[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const unsigned long long i = base + (unsigned long long)(u * G + lane);
+        const uint32_t w = i < e ? snp_word<CNT>(P, bins, (uint32_t)i) : 0u;
+        k2[u] = bin_k2(w); g1[u] = bin_g1(w); g2[u] = bin_g2(w);
+        x2[u] = xa[u] = xb[u] = 0u;
+      }
+      for (int turn = 0; turn < G / WAVE; ++turn) {
+        if (wv == turn) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            if (k2[u]) x2[u] = h2_take<P16>(H2, k2[u]);
+            if (g1[u]) xa[u] = atomicExch(&H1a[g1[u] * S1], 0u);
+            if (g2[u]) xb[u] = atomicExch(&H1b[g2[u] * S1], 0u);
+          }
+        }
+        __syncthreads();
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (x2[u]) term(x2[u], (int)k2[u], N2, hb.B2, s2, q2);
+        if (xa[u]) term(xa[u], P.t1a + (int)g1[u], N1a, hb.B1a, sa, qa);
+        if (xb[u]) term(xb[u], P.t1b + (int)g2[u], N1b, hb.B1b, sb, qb);
+      }
+    }
+  } else {
   for (uint32_t i = b + lane; i < e; i += G) {
     const uint32_t w = snp_word<CNT>(P, bins, i);
     const uint32_t k2 = bin_k2(w), g1 = bin_g1(w), g2 = bin_g2(w);
@@ -1740,6 +1781,7 @@ __device__ __forceinline__ WinOut eval_exact(const KParams& P, const uint32_t* _
         qb &= prop_ok(x, N1b, t.v, hb.B1b, floatv);
       }
     }
+  }
   }
   s2 = group_sum_d<G>(s2, redd, 0);
   sa = group_sum_d<G>(sa, redd, 1);
