@@ -213,6 +213,7 @@ struct sfs2d_plan {
   bool fst_scan = false;          // Fst summed by k_scan_w itself (counts plans, small grids): k_prep has no Fst work
   bool fst_mask = true;           // Fst in the scan: the data set has SNPs with < 2 called alleles (k_scan_w FST 3 / 5)
   bool gate = false;              // Fst in the scan, folded, called counts within (n1, n2): k_scan_w's GATE variants
+  bool lean = false;              // gate, fixed-bp slot records, n1p, n2p <= 31: k_scan_w's LEAN variants (same results)
   int nfst = 0;                   // k_bg_slice's extra Fst workgroups
   // bootstrap null (sfs2d_plan_null_run): the last call's task table and records
   std::vector<NullTask> ntask_h;
@@ -293,10 +294,10 @@ void set_variant(sfs2d_plan* pl, int p16, int fused, int fst, int cnt, int gate,
   pl->variant_set = true;
 }
 
-template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false>
+template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false, bool LEAN = false>
 void launch_scan_w(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
-  set_variant(pl, P16, FUSED, FST, CNT, GATE, -1);
-  hipExtLaunchKernelGGL((k_scan_w<P16, FUSED, FST, CNT, GATE>), dim3((unsigned)pl->chunks.size()), dim3(SBLOCK), pl->scan_lds,
+  set_variant(pl, P16, FUSED, FST, CNT, GATE, -1);   // (LEAN: a gated variant, gate = 1)
+  hipExtLaunchKernelGGL((k_scan_w<P16, FUSED, FST, CNT, GATE, LEAN>), dim3((unsigned)pl->chunks.size()), dim3(SBLOCK), pl->scan_lds,
                      CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_lp, pl->d_head,
                      per_chrom, pl->ctx->d_lnx, pl->ctx->d_df, out, pl->d_err, bp, pl->d_repl, pl->d_bcount,
                      plan_par(pl), pl->d_leaves, pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels,
@@ -340,7 +341,15 @@ hipError_t launch_scan_c(sfs2d_plan* pl, sfs2d_window* out) {
   } else if (pl->G == WAVE) {
     if constexpr (CNT) {
       if (pl->fst_scan) {
-        if (pl->gate) {   // (no SNP's key can leave the inner grid: the variants without the range test)
+        if (pl->lean) {   // (gated, and the window loop's tail specialised for fixed-bp slots and n1p, n2p <= 31)
+          if (pl->fst_mask) {
+            if (pl->fused) launch_scan_w<P16, true, 3, CNT, true, true>(pl, out, per_chrom, bp);
+            else launch_scan_w<P16, false, 3, CNT, true, true>(pl, out, per_chrom, bp);
+          } else {
+            if (pl->fused) launch_scan_w<P16, true, 2, CNT, true, true>(pl, out, per_chrom, bp);
+            else launch_scan_w<P16, false, 2, CNT, true, true>(pl, out, per_chrom, bp);
+          }
+        } else if (pl->gate) {   // (no SNP's key can leave the inner grid: the variants without the range test)
           if (pl->fst_mask) {
             if (pl->fused) launch_scan_w<P16, true, 3, CNT, true>(pl, out, per_chrom, bp);
             else launch_scan_w<P16, false, 3, CNT, true>(pl, out, per_chrom, bp);
@@ -1153,6 +1162,10 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // last bin -- so the scan's per-SNP range test on it is dead (k_scan_w's GATE variants, built for Fst in
   // the scan).  Over-called or unfolded data keep the test.
   pl->gate = pl->fst_scan && prm->fold && nc_ok;
+  // gated plans whose windows come from fixed-bp slot records and whose folded 1D spectra fit one half-wave
+  // each: the LEAN variants (SFS2D_LEAN=0: the gated variants, for comparison -- the results are the same)
+  pl->lean = pl->gate && bp && K.n1p <= 31 && K.n2p <= 31;
+  if (const char* ev = std::getenv("SFS2D_LEAN")) pl->lean = pl->lean && ev[0] != '0';
   const PwTree pw = pw_plan(K.nb2 - 3);
   pl->fst_mask = data->low_nc;
   pl->fst_win = pl->sliced && bp && pl->fst && !pl->fst_scan;
@@ -1179,6 +1192,10 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
                           (const void*)k_scan_w<true, false, 2, true, true>, (const void*)k_scan_w<false, false, 2, true, true>,
                           (const void*)k_scan_w<true, true, 3, true, true>, (const void*)k_scan_w<false, true, 3, true, true>,
                           (const void*)k_scan_w<true, false, 3, true, true>, (const void*)k_scan_w<false, false, 3, true, true>,
+                          (const void*)k_scan_w<true, true, 2, true, true, true>, (const void*)k_scan_w<false, true, 2, true, true, true>,
+                          (const void*)k_scan_w<true, false, 2, true, true, true>, (const void*)k_scan_w<false, false, 2, true, true, true>,
+                          (const void*)k_scan_w<true, true, 3, true, true, true>, (const void*)k_scan_w<false, true, 3, true, true, true>,
+                          (const void*)k_scan_w<true, false, 3, true, true, true>, (const void*)k_scan_w<false, false, 3, true, true, true>,
                           (const void*)k_scan_g<true, false, false>, (const void*)k_scan_g<false, false, false>,
                           (const void*)k_scan_g<true, true, false>, (const void*)k_scan_g<false, true, false>,
                           (const void*)k_scan_g<true, false, true>, (const void*)k_scan_g<false, false, true>,
@@ -1206,6 +1223,12 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     else if (pl->gw)
       oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<true, true, true>, WAVE, pl->scan_lds)
                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<false, true, true>, WAVE, pl->scan_lds);
+    else if (pl->lean && pl->fused)
+      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, true, 2, true, true, true>, SBLOCK, pl->scan_lds)
+                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, true, 2, true, true, true>, SBLOCK, pl->scan_lds);
+    else if (pl->lean)
+      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, false, 2, true, true, true>, SBLOCK, pl->scan_lds)
+                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, false, 2, true, true, true>, SBLOCK, pl->scan_lds);
     else if (pl->gate && pl->fused)
       oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, true, 2, true, true>, SBLOCK, pl->scan_lds)
                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, true, 2, true, true>, SBLOCK, pl->scan_lds);

@@ -2613,13 +2613,19 @@ __device__ __forceinline__ void lds_copy_d(double* dst, const double* __restrict
 // and two wave sums per window: k_prep then runs without the Fst work (DESIGN.md "Fst placement");
 // 3: as 2, for data sets where some SNP has < 2 called alleles in a population (those SNPs masked out)
 // GATE: cls_k2g's (the per-SNP key needs no range test; the host selects it from the data's largest counts)
-template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false>
+// LEAN (GATE plans with fixed-bp slot records and n1p, n2p <= 31 -- the headline class): mode_bp, half1d, filt
+// and the last-bin rule are compile-time constants, so the general 1D end pass, the five wave_sum_all sums and
+// the nlast / nvar pass are not in the kernel; the ln-of-totals loads are issued as soon as their counts are
+// known; P16: the batch's counts are stored unclamped (a window holds < 65536 SNPs).  Same bits as GATE alone.
+template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false, bool LEAN = false>
 // (wgi: the work item -- chunks[wgi] -- and nwg the items of the launch: k_scan_w's block index and grid)
 __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_t nwg, SCAN_W_ARGS) {
   constexpr bool FSTIN = FST >= 2;
   constexpr bool FMASK = FST == 3;
   static_assert(!FSTIN || CNT, "Fst in the scan reads the counts");
   static_assert(!GATE || CNT, "the gate is a property of the counts the scan classifies");
+  static_assert(!LEAN || (GATE && FSTIN), "the lean window loop is built for the gated Fst-in-scan plans");
+  if (LEAN) mode_bp = 1;   // (the lean class has fixed-bp slot records)
   constexpr int DT = LNT;   // D(r) entries in LDS
   constexpr int R1U = R1;
   constexpr int NWV = SBLOCK / WAVE;
@@ -2788,8 +2794,8 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       for (int c = tid; c < P.nchrom; c += SBLOCK) bcount[(size_t)(1 - par) * P.nchrom + c] = 0u;
   }
   if (!active) return;
-  const bool filt = P.ann_want >= 0;
-  const bool half1d = P.n1p <= 31 && P.n2p <= 31;   // bins 0..n_p of each population on lanes 0-31 / 32-63
+  const bool filt = LEAN ? false : P.ann_want >= 0;
+  const bool half1d = LEAN ? true : P.n1p <= 31 && P.n2p <= 31;   // bins 0..n_p of each population on lanes 0-31 / 32-63
   const uint32_t zflags = bg_zero_flags(hb);
   const bool nan2 = hb.flags & BGF_NAN2, nan1a = hb.flags & BGF_NAN1A, nan1b = hb.flags & BGF_NAN1B;
   uint32_t* const H1a_l = H1a + rep;   // this lane's replica column of the 1D histograms
@@ -2898,14 +2904,18 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
     }
     jb = 0;
   };
+  // (LEAN P16: no window holds 65,536 SNPs -- the host's p16 condition -- and every count is at most the
+  // window's SNPs, so the saturation is the identity; nsnp = 0xffff still takes flush's exact path)
+  // (a macro: the frontend folds the constant condition, and the other variants' code stays as it was)
+#define SAT16(x) ((LEAN && P16) ? (x) : min((x), 0xffffu))
   // window jb of the batch: its integers (lane 0)
   auto put_u = [&](uint32_t slot, uint32_t b, uint32_t nsnp, uint32_t n2, uint32_t n1a, uint32_t n1b, uint32_t nvar,
                    uint32_t nlast) {
     sh_bu[wv][0][jb] = slot;
     sh_bu[wv][1][jb] = b;
-    sh_bu[wv][2][jb] = min(n2, 0xffffu) | (min(n2 + nlast, 0xffffu) << 16);
-    sh_bu[wv][3][jb] = min(n1a, 0xffffu) | (min(n1b, 0xffffu) << 16);
-    sh_bu[wv][4][jb] = min(nsnp, 0xffffu) | (min(nvar, 0xffffu) << 16);
+    sh_bu[wv][2][jb] = SAT16(n2) | (SAT16(n2 + nlast) << 16);
+    sh_bu[wv][3][jb] = SAT16(n1a) | (SAT16(n1b) << 16);
+    sh_bu[wv][4][jb] = SAT16(nsnp) | (SAT16(nvar) << 16);
   };
   auto put = [&](uint32_t slot, uint32_t b, uint32_t nsnp, uint32_t n2, uint32_t n1a, uint32_t n1b, uint32_t nvar,
                  uint32_t nlast, double s2, double sa, double sb, ulonglong2 fq) {
@@ -3160,7 +3170,7 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
     // variant_type filter (nvar).  Folded counts plans of nc_ok data skip it.  (GATE is chosen for such plans
     // only and never enters: it tests fold / filt alone, which leaves the benchmarked variants' code and
     // registers as measured -- without the pass two of them allocate one VGPR less.)
-    if (GATE ? (!P.fold || filt) : (!P.fold || !CNT || !P.nc_ok)) {
+    if (!LEAN && (GATE ? (!P.fold || filt) : (!P.fold || !CNT || !P.nc_ok))) {
       for (uint32_t i0 = cur.b; i0 < cur.e; i0 += WAVE) {   // wave-uniform trip count
         const uint32_t w = i0 + lane < cur.e ? snp_word<CNT>(P, bins, i0 + lane) : 0u;
         nlast += __popcll(__ballot((w & B_LAST) != 0u));
@@ -3170,6 +3180,11 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
     if (!filt) nvar = nsnp;
     ulonglong2 fq = make_ulonglong2(0ull, 0ull);   // this window's Fst sums (k_prep): their latency under the window
     if (FST == 1 && lane == 0) fq = reinterpret_cast<const ulonglong2*>(fsum)[s];
+    // LEAN: ln of the window's totals, each (scalar) load issued as soon as its count is known -- n2 here, n1a /
+    // n1b after the 1D pass -- and first read after put5, so that the scalar-cache round trips pass under the 1D
+    // pass and the wave sums.  They wait in fq and accb, which this class does not use: a local of their own
+    // changed the register allocation of the other variants' streamed-row loop.
+    if (LEAN) fq.x = (unsigned long long)__double_as_longlong(lnx[SAT16(n2)]);
     if (it == 0) STAMP(12);
     MARK(23);
     group_sync<WAVE>();
@@ -3242,6 +3257,10 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       n1a = slots - (uint32_t)__builtin_amdgcn_readlane((int)xa[0], 0) - ea;
       n1b = slots - (uint32_t)__builtin_amdgcn_readlane((int)xb[0], 0) - eb;
     }
+    if (LEAN) {
+      fq.y = (unsigned long long)__double_as_longlong(lnx[SAT16(n1a)]);
+      accb = lnx[SAT16(n1b)];
+    }
     if (it == 0) STAMP(13);
     MARK(25);
     // the sums, replicated in every lane (fixed trees: deterministic), into lane jb of the batch
@@ -3252,7 +3271,12 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       MARK(26);
       put5(v, fq);
       if (lane == 0) put_u(s, cur.b, nsnp, n2, n1a, n1b, nvar, nlast);
-      if ((uint32_t)lane == jb) {
+      if (LEAN && (uint32_t)lane == jb) {
+        fl2 = __longlong_as_double((long long)fq.x);
+        fla = __longlong_as_double((long long)fq.y);
+        flb = accb;
+      }
+      if (!LEAN && (uint32_t)lane == jb) {
         fl2 = lnx[min(n2, 0xffffu)];
         fla = lnx[min(n1a, 0xffffu)];
         flb = lnx[min(n1b, 0xffffu)];
@@ -3293,13 +3317,14 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
   __builtin_amdgcn_s_barrier();   // diagnostic build only: the block's end is its last active wave's
 #endif
   BLK_STAMP(1, 1);
+#undef SAT16
 }
 
 // CNT: `bins` is the counts array (counts plans): every scan classifies the counts it streams
-template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false>
+template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false, bool LEAN = false>
 __global__ __launch_bounds__(SBLOCK) __attribute__((amdgpu_waves_per_eu(4))) void k_scan_w(SCAN_W_ARGS) {
   extern __shared__ double ldsd[];
-  scan_w_small<P16, FUSED, FST, CNT, GATE>(ldsd, blockIdx.x, gridDim.x, SCAN_W_PASS);
+  scan_w_small<P16, FUSED, FST, CNT, GATE, LEAN>(ldsd, blockIdx.x, gridDim.x, SCAN_W_PASS);
 }
 
 // K3 for large grids, one wavefront per window (LDS: the wave's histograms only)
