@@ -1972,8 +1972,9 @@ int null_tables(sfs2d_plan* pl) {
   return 0;
 }
 
+// block == 1: k_null; a longer block: k_null_blk (the same LDS layout, workgroup and grid)
 template <bool P16, bool CNT>
-int launch_null(sfs2d_plan* pl, uint32_t R, unsigned long long nrec, uint2 key, sfs2d_window* out) {
+int launch_null(sfs2d_plan* pl, uint32_t R, unsigned long long nrec, uint2 key, uint32_t block, sfs2d_window* out) {
   sfs2d_ctx* ctx = pl->ctx;
   const KParams& K = pl->K;
   // wavefronts per workgroup from the LDS a wave's histograms need: as many as fit 64 KB, at most 8
@@ -1981,18 +1982,24 @@ int launch_null(sfs2d_plan* pl, uint32_t R, unsigned long long nrec, uint2 key, 
   const int wpb = (int)std::max<size_t>(1, std::min<size_t>(NULL_MAX_WAVES, (64 * 1024) / per));
   const size_t lds = per * wpb;
   if (lds > 160 * 1024) return set_err(ctx, SFS2D_E_ARG, "2D grid too large for k_null's LDS histogram");
-  const void* f = (const void*)k_null<P16, CNT>;
+  const void* f = block == 1u ? (const void*)k_null<P16, CNT> : (const void*)k_null_blk<P16, CNT>;
   if (lds > 64 * 1024) HIPCHK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_null<P16, CNT>, wpb * WAVE, lds) != hipSuccess || occ < 1) {
+  const hipError_t oe = block == 1u ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_null<P16, CNT>, wpb * WAVE, lds)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_null_blk<P16, CNT>, wpb * WAVE, lds);
+  if (oe != hipSuccess || occ < 1) {
     (void)hipGetLastError();
     occ = 1;
   }
   // one resident set of workgroups striding over the records (a wave zeroes its histograms once)
   const unsigned long long want = (nrec + wpb - 1) / wpb;
   const unsigned grid = (unsigned)std::min<unsigned long long>(want, (unsigned long long)occ * ctx->ncu);
-  hipLaunchKernelGGL((k_null<P16, CNT>), dim3(grid), dim3(wpb * WAVE), lds, CTX_STREAM(ctx), K, scan_src(pl), pl->d_ntask, R,
-                     nrec, key, pl->d_tab, pl->d_head, pl->do_bg ? 1 : 0, ctx->d_lnx, out);
+  if (block == 1u)
+    hipLaunchKernelGGL((k_null<P16, CNT>), dim3(grid), dim3(wpb * WAVE), lds, CTX_STREAM(ctx), K, scan_src(pl), pl->d_ntask, R,
+                       nrec, key, pl->d_tab, pl->d_head, pl->do_bg ? 1 : 0, ctx->d_lnx, out);
+  else
+    hipLaunchKernelGGL((k_null_blk<P16, CNT>), dim3(grid), dim3(wpb * WAVE), lds, CTX_STREAM(ctx), K, scan_src(pl),
+                       pl->d_ntask, R, nrec, key, block, pl->d_tab, pl->d_head, pl->do_bg ? 1 : 0, ctx->d_lnx, out);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
@@ -2002,10 +2009,17 @@ int launch_null(sfs2d_plan* pl, uint32_t R, unsigned long long nrec, uint2 key, 
 
 int sfs2d_plan_null_run(sfs2d_plan* pl, const sfs2d_null_params* np, const int64_t* tasks, int64_t ntasks,
                         sfs2d_window* out_dev) {
+  return sfs2d_plan_null_run_blocks(pl, np, 1, tasks, ntasks, out_dev);
+}
+
+int sfs2d_plan_null_run_blocks(sfs2d_plan* pl, const sfs2d_null_params* np, int64_t block, const int64_t* tasks,
+                               int64_t ntasks, sfs2d_window* out_dev) {
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   const sfs2d_data* d = pl->data;
   if (!np || ntasks < 0 || (ntasks > 0 && !tasks)) return set_err(ctx, SFS2D_E_ARG, "null argument");
+  if (block < 1 || block > 0xffffffffll)
+    return set_err(ctx, SFS2D_E_ARG, "null run: block length " + std::to_string(block) + " must be in [1, 2^32)");
   if (pl->base) return set_err(ctx, SFS2D_E_ARG, "null run on an attached plan: use its base plan (same data, same tables)");
   if (pl->runs == 0) return set_err(ctx, SFS2D_E_ARG, "null run before the plan's first run (no background tables yet)");
   if (np->replicates < 1) return set_err(ctx, SFS2D_E_ARG, "null run: replicates must be >= 1");
@@ -2057,9 +2071,12 @@ int sfs2d_plan_null_run(sfs2d_plan* pl, const sfs2d_null_params* np, const int64
   HIPCHK(ctx, hipMemcpyAsync(pl->d_ntask, pl->ntask_h.data(), sizeof(NullTask) * (size_t)ntasks, hipMemcpyHostToDevice, st));
   const uint2 key = make_uint2((uint32_t)np->seed, (uint32_t)(np->seed >> 32));
   // u16-packed 2D bins while no bin can hold 65536 draws
+  const uint32_t blk = (uint32_t)block;
   if (maxm <= 65535u)
-    return pl->cnt ? launch_null<true, true>(pl, np->replicates, nrec, key, out) : launch_null<true, false>(pl, np->replicates, nrec, key, out);
-  return pl->cnt ? launch_null<false, true>(pl, np->replicates, nrec, key, out) : launch_null<false, false>(pl, np->replicates, nrec, key, out);
+    return pl->cnt ? launch_null<true, true>(pl, np->replicates, nrec, key, blk, out)
+                   : launch_null<true, false>(pl, np->replicates, nrec, key, blk, out);
+  return pl->cnt ? launch_null<false, true>(pl, np->replicates, nrec, key, blk, out)
+                 : launch_null<false, false>(pl, np->replicates, nrec, key, blk, out);
 }
 
 int sfs2d_plan_null_read(sfs2d_plan* pl, sfs2d_window* out_host, int64_t cap, int64_t* nrec_out) {

@@ -43,6 +43,7 @@ EXPORTS = [
     "sfs2d_data_read", "sfs2d_plan_run_streams", "sfs2d_ctx_use_own_stream", "sfs2d_bg_hist_dev", "sfs2d_plan_bg_rows_dev", "sfs2d_plan_bg_rows_set_dev",
     "sfs2d_ctx_get_stream", "sfs2d_plan_set_fst_out", "sfs2d_graph_create", "sfs2d_graph_launch", "sfs2d_graph_destroy",
     "sfs2d_plan_create_sliding", "sfs2d_plan_attach_sliding", "sfs2d_plan_null_run", "sfs2d_plan_null_read",
+    "sfs2d_plan_null_run_blocks",
     "sfs2d_plan_scan_variant",
 ]
 ABI_VERSION = 2   # SFS2D_ABI_VERSION of include/sfs2d.h
@@ -148,6 +149,7 @@ def lib():
     L.sfs2d_plan_create_sliding.argtypes = [vp, vp, C.POINTER(Params), i64, C.POINTER(vp)]
     L.sfs2d_plan_attach_sliding.argtypes = [vp, C.POINTER(Params), i64, C.POINTER(vp)]
     L.sfs2d_plan_null_run.argtypes = [vp, C.POINTER(NullParams), vp, i64, vp]
+    L.sfs2d_plan_null_run_blocks.argtypes = [vp, C.POINTER(NullParams), i64, vp, i64, vp]
     L.sfs2d_plan_null_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sfs2d_data_synth_sims.argtypes = [vp, C.POINTER(SynthParams), vp, vp, i32, vp, i32, C.POINTER(vp)]
     L.sfs2d_data_read.argtypes = [vp, vp, vp, i64]

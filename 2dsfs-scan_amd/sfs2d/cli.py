@@ -22,6 +22,8 @@ multi_sliding_scan): ``<prefix>_20kb_step5kb.csv`` with the same columns, clean 
 ``--null-replicates R [--null-seed S] [--null-sizes exact]`` appends six bootstrap p-value columns
 (``p_T2D`` ... ``p_T2D_diff``, after ``FST`` when present) to every output file: R windows of the same
 SNP count drawn from the window's chromosome per size class (scan_pvalues).
+``--null-block B|window`` (with ``--null-replicates``) draws runs of B consecutive SNPs instead of single
+SNPs, so that the null keeps the chromosome's linkage; ``window``: one run as long as the window.
 """
 from __future__ import annotations
 
@@ -98,6 +100,9 @@ def main(argv=None):
     ap.add_argument("--null-seed", type=int, default=0, metavar="S")
     ap.add_argument("--null-sizes", choices=["exact"], default=None,
                     help="exact: a null for every distinct SNP count (default: a 9 %% geometric grid of sizes)")
+    ap.add_argument("--null-block", default=None, metavar="B|window",
+                    help="resample runs of B consecutive SNPs (window: one run per replicate window) instead of "
+                         "single SNPs; needs --null-replicates")
     ap.add_argument("--out-prefix", default="stats")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="VCF parser threads (0 = all)")
@@ -107,7 +112,20 @@ def main(argv=None):
     if a.null_replicates is not None and a.null_replicates < 1:
         ap.error("--null-replicates must be >= 1")
     null = a.null_replicates is not None
-    nkw = dict(replicates=a.null_replicates, seed=a.null_seed, sizes=a.null_sizes)
+    block = None
+    if a.null_block is not None:
+        if not null:
+            ap.error("--null-block needs --null-replicates")
+        if a.null_block == "window":
+            block = "window"
+        else:
+            try:
+                block = int(a.null_block)
+            except ValueError:
+                block = 0
+            if not 1 <= block < (1 << 32):
+                ap.error("--null-block must be an integer in [1, 2^32) or 'window'")
+    nkw = dict(replicates=a.null_replicates, seed=a.null_seed, sizes=a.null_sizes, block=block)
     if a.step is not None:
         if a.snp_window:
             ap.error("--step applies to fixed-bp windows: not with --snp-window")

@@ -286,14 +286,17 @@ class Plan:
         self.eng.check(self.eng.lib.sfs2d_plan_read(self.h, L.ptr(out), self.nrec, C.byref(n)))
         return out
 
-    def null_run(self, tasks, replicates: int, seed: int, out_dev_ptr: Optional[int] = None):
+    def null_run(self, tasks, replicates: int, seed: int, out_dev_ptr: Optional[int] = None, block: int = 1):
         """The bootstrap null of this plan's last run (sfs2d_plan_null_run): ``tasks`` = (pool, m) pairs
         (pool: a chromosome index, or -1 = all SNPs on a supplied-background plan), ``replicates`` windows
         of m SNPs drawn with replacement from the pool per task, evaluated against the pool's background.
         Record t * replicates + r is replicate r of task t.  The tasks are split over calls of at most
         2**22 records; with ``out_dev_ptr`` (a device buffer of len(tasks) * replicates records) nothing
-        is copied to the host, else ``null_read`` returns the records."""
+        is copied to the host, else ``null_read`` returns the records.  ``block`` > 1: the block null
+        (sfs2d_plan_null_run_blocks) -- runs of ``block`` consecutive SNPs of the circular pool are drawn
+        instead of single SNPs, the last run cut at m; any block >= m is one run of m SNPs."""
         from .null import MAX_CALL_RECORDS
+        block = int(block)
         tk = np.ascontiguousarray(np.asarray(list(tasks), np.int64).reshape(-1, 2))
         R = int(replicates)
         if R < 0 or R > 0xFFFFFFFF:
@@ -305,7 +308,11 @@ class Plan:
         for a in range(0, nt, per):
             part = np.ascontiguousarray(tk[a:a + per])
             out = C.c_void_p(out_dev_ptr + a * R * L.WINDOW_DTYPE.itemsize) if out_dev_ptr else None
-            self.eng.check(self.eng.lib.sfs2d_plan_null_run(self.h, C.byref(npar), L.ptr(part), len(part), out))
+            if block == 1:
+                rc = self.eng.lib.sfs2d_plan_null_run(self.h, C.byref(npar), L.ptr(part), len(part), out)
+            else:
+                rc = self.eng.lib.sfs2d_plan_null_run_blocks(self.h, C.byref(npar), block, L.ptr(part), len(part), out)
+            self.eng.check(rc)
             self._null_call_n = len(part) * R
             if not out_dev_ptr and nt > per:   # the plan-owned buffer holds one call's records
                 self._null_parts.append(self._null_read_call())

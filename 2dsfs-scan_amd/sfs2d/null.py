@@ -7,7 +7,8 @@ evaluated against the same background table.  The device draws and evaluates the
 
 * ``size_classes`` -- the window sizes that get a null of their own (a window uses the smallest
   class >= its size);
-* ``draw_indices`` -- the bit-exact host twin of the device's draws (``synth._philox``);
+* ``draw_indices`` -- the bit-exact host twin of the device's draws (``synth._philox``), single SNPs or
+  blocks of consecutive SNPs (``block``: kernel k_null_blk, a null that keeps the pool's linkage);
 * ``resample`` -- the replicate windows materialised as a ``PackedSNPs`` (for a CPU checker);
 * ``pvalues`` -- the p-value definition in numpy; ``pvalues_device`` -- the same counts taken with
   torch sort / searchsorted over the record buffer in HBM.
@@ -74,22 +75,33 @@ def _mulhi64(x: np.ndarray, n: int) -> np.ndarray:
     return (hi * n + ((lo * n) >> np.uint64(32))) >> np.uint64(32)
 
 
-def draw_indices(seed: int, pool_id: int, lo: int, n: int, m: int, replicates: int) -> np.ndarray:
+def draw_indices(seed: int, pool_id: int, lo: int, n: int, m: int, replicates: int, block: int = 1) -> np.ndarray:
     """SNP indices of the ``replicates`` windows of task (pool_id, m): int64 [replicates, m].  Draw j of
     replicate r: c = philox4x32((j >> 1, r, m, pool_id + 1), (seed lo, seed hi)); x64 = c0 | c1 << 32 for
     even j, c2 | c3 << 32 for odd j; index = lo + mulhi64(x64, n).  A function of (seed, pool_id, m, r, j)
-    alone -- what k_null computes."""
+    alone -- what k_null computes.
+    ``block`` = b > 1 (the block null, k_null_blk): that value is the start s_i of block i, for
+    i < ceil(m / b) (b is not part of the counter), and draw j = i * b + k, k < b, is
+    lo + (s_i + k) mod n -- runs of b consecutive SNPs of the circular pool, the last one cut at m."""
     if not (1 <= n < (1 << 32)) or m < 1 or replicates < 1:
         raise ValueError("draw_indices: 1 <= n < 2**32, m >= 1, replicates >= 1")
-    j = np.arange(m, dtype=np.uint64)[None, :]
+    if not (1 <= block < (1 << 32)):
+        raise ValueError("draw_indices: 1 <= block < 2**32")
+    b = int(block)
+    nblk = -(-m // b)
+    i = np.arange(nblk, dtype=np.uint64)[None, :]
     r = np.arange(replicates, dtype=np.uint64)[:, None]
-    q = np.broadcast_to(j >> np.uint64(1), (replicates, m))
-    rr = np.broadcast_to(r, (replicates, m))
+    q = np.broadcast_to(i >> np.uint64(1), (replicates, nblk))
+    rr = np.broadcast_to(r, (replicates, nblk))
     c0, c1, c2, c3 = _philox(q, rr, np.uint64(m & 0xFFFFFFFF), np.uint64((pool_id + 1) & 0xFFFFFFFF),
                              seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-    even = (j & np.uint64(1)) == 0
+    even = (i & np.uint64(1)) == 0
     x = np.where(even, c0 | (c1 << np.uint64(32)), c2 | (c3 << np.uint64(32)))
-    return (np.uint64(lo) + _mulhi64(x, n)).astype(np.int64)
+    s = _mulhi64(x, n)
+    if b > 1:
+        j = np.arange(m, dtype=np.uint64)
+        s = (s[:, j // np.uint64(b)] + (j % np.uint64(b))[None, :]) % np.uint64(n)   # (s + k < 2**33)
+    return (np.uint64(lo) + s).astype(np.int64)
 
 
 def pool_range(p: PackedSNPs, pool: int):
@@ -101,18 +113,18 @@ def pool_range(p: PackedSNPs, pool: int):
     return int(p.chrom_off[pool]), int(p.chrom_off[pool + 1] - p.chrom_off[pool])
 
 
-def resample(p: PackedSNPs, tasks, replicates: int, seed: int):
+def resample(p: PackedSNPs, tasks, replicates: int, seed: int, block: int = 1):
     """The replicate windows of ``tasks`` ((pool, m) pairs) as a data set: (PackedSNPs q, wins) with
     wins[t * replicates + r] = (pool, r, begin, end), SNPs [begin, end) of q being replicate r of task t
     (each drawn SNP with its own counts, position and annotation; one pseudo-chromosome per task).  For a
     CPU checker of the device records (tests: oracle.window_records(q, wins, ...)); the device never
-    materialises these windows."""
+    materialises these windows.  ``block``: the block length of ``draw_indices``."""
     idx, wins, offs = [], [], [0]
     for pool, m in tasks:
         lo, n = pool_range(p, int(pool))
         if n == 0:
             raise ValueError(f"pool {pool} is empty")
-        d = draw_indices(seed, int(pool), lo, n, int(m), replicates)
+        d = draw_indices(seed, int(pool), lo, n, int(m), replicates, block)
         for r in range(replicates):
             b = offs[-1] + r * int(m)
             wins.append((int(pool), r, b, b + int(m)))

@@ -432,11 +432,12 @@ class LikelihoodInference_jointSFS:
         return out
 
     # ------------------------------------------------------------------ bootstrap null (extension)
-    def _null_columns(self, p, base, items, replicates, seed, sizes, pool=None):
+    def _null_columns(self, p, base, items, replicates, seed, sizes, pool=None, block=1):
         """Add the six p_* keys to every row of ``items`` ([(records, record labels, rows)] of plans that
         share ``base``'s data and tables): one null run on ``base`` over the union of the (pool, size class)
         pairs of all windows, the exceedance counts taken on the device (sfs2d.null.pvalues_device).
-        pool: the background chromosome of every window (None: each window's own chromosome)."""
+        pool: the background chromosome of every window (None: each window's own chromosome); block: the
+        null's block length (1: single SNPs)."""
         import torch
         from sfs2d import null as N
         sel = []
@@ -454,7 +455,7 @@ class LikelihoodInference_jointSFS:
         eng = base.eng
         buf = torch.empty(len(tasks) * R * L.WINDOW_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{self.device}")
         torch.cuda.synchronize(buf.device)   # (the engine's stream is ordered against nothing of torch's)
-        base.null_run(tasks, R, seed, out_dev_ptr=buf.data_ptr())
+        base.null_run(tasks, R, seed, out_dev_ptr=buf.data_ptr(), block=block)
         h = eng.stream_handle()
         if h:
             torch.cuda.ExternalStream(h, device=buf.device).synchronize()
@@ -469,8 +470,22 @@ class LikelihoodInference_jointSFS:
                     rows[lb][key] = None if np.isnan(v) else float(v)
                 k += 1
 
+    @staticmethod
+    def _null_block(block):
+        """scan_pvalues' ``block`` as a block length: None -> 1, "window" -> 2**32 - 1 (longer than any class),
+        an int in [1, 2**32) -> itself."""
+        if block is None:
+            return 1
+        if isinstance(block, str):
+            if block != "window":
+                raise ValueError(f"block must be None, an int >= 1 or 'window', got {block!r}")
+            return 0xFFFFFFFF
+        if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or not 1 <= int(block) < (1 << 32):
+            raise ValueError(f"block must be None, an int in [1, 2**32) or 'window', got {block!r}")
+        return int(block)
+
     def scan_pvalues(self, data_dict, window_sizes=(), snp_window_sizes=(), step_size=None,
-                     background_chromosome=None, replicates=999, seed=0, sizes=None, fst=False):
+                     background_chromosome=None, replicates=999, seed=0, sizes=None, fst=False, block=None):
         """The scans of ``multi_scan`` (``step_size`` given: ``multi_sliding_scan``) with a bootstrap p-value
         beside every statistic: each row additionally holds p_T2D, p_T1D_pop1, p_T1D_pop2, p_new_term_pop1,
         p_new_term_pop2 and p_T2D_diff -- the share of ``replicates`` windows of the same number of SNPs
@@ -479,6 +494,10 @@ class LikelihoodInference_jointSFS:
         (definition, what the null does not model).  The p-values of the derived
         terms are formed from the window's own three T's (None when one is None), not from
         combined_scan's carried values.  One null run per call serves every window size.
+        ``block``: None or 1 draws single SNPs (no linkage: p-values of linked data are anti-conservative);
+        an int b > 1 draws runs of b consecutive SNPs of the (circular) chromosome, the last one cut at the
+        class size; "window" makes every run as long as its class -- a random placement of a window of
+        that many SNPs on the chromosome ("blocks").
         ``background_chromosome``: one window size, scanned as scan_chooseChr (or scan_chooseChr_bySNPs for a
         SNP-count size, sliding_scan with ``step_size``) does; that chromosome is every window's pool; the
         result is {size: rows}.  Not in the reference (it thresholds by SNP-count quantile and top 1 % in R,
@@ -489,9 +508,10 @@ class LikelihoodInference_jointSFS:
             raise ValueError(f"replicates must be >= 1, got {replicates}")
         if sizes is not None and sizes != "exact":
             sizes = sorted(int(x) for x in sizes)
+        block = self._null_block(block)
 
         def hook(pool=None):
-            return lambda p, base, items: self._null_columns(p, base, items, replicates, seed, sizes, pool)
+            return lambda p, base, items: self._null_columns(p, base, items, replicates, seed, sizes, pool, block)
         if background_chromosome is None:
             if step_size is None:
                 return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, hook())
@@ -533,7 +553,7 @@ class LikelihoodInference_jointSFS:
                 else:
                     rows = post.fixed_bg_scan(recs, p, w, post.num_slots(recs))
                 labels = post.record_labels(recs, p, "snps" if snps else "bp", w, step)
-                self._null_columns(p, pl, [(recs, labels, rows)], replicates, seed, sizes, pool=bgc)
+                self._null_columns(p, pl, [(recs, labels, rows)], replicates, seed, sizes, pool=bgc, block=block)
             finally:
                 pl.close()
         finally:

@@ -38,7 +38,8 @@ extern "C" {
  * sfs2d_ctx_use_own_stream / sfs2d_ctx_get_stream added, the sfs2d_dist_* entry points removed;
  * sfs2d_graph_* added (round 6, additive); sfs2d_plan_create_sliding / sfs2d_plan_attach_sliding added
  * (additive: sfs2d_params keeps its layout, the step is an argument); sfs2d_plan_null_run / _null_read added
- * (additive) */
+ * (additive); sfs2d_plan_null_run_blocks added (additive: sfs2d_null_params keeps its layout, the block length is
+ * an argument) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -289,6 +290,20 @@ int sfs2d_plan_attach_sliding(sfs2d_plan* base, const sfs2d_params* params, int6
 typedef struct { uint64_t seed; uint32_t replicates; } sfs2d_null_params;
 int sfs2d_plan_null_run(sfs2d_plan* plan, const sfs2d_null_params* np, const int64_t* tasks, int64_t ntasks,
                         sfs2d_window* out_dev);
+/* The block null: sfs2d_plan_null_run with runs of consecutive SNPs resampled instead of single SNPs, so that a
+ * replicate window keeps the linkage of its pool ("blocks").  One block length `block` for
+ * the call, 1 <= block < 2^32.  Task (pool, m), pool range [lo, lo + n), replicate r: nblk = ceil(m / block)
+ * blocks; block i starts at s_i = mulhi64(x64, n), x64 being what draw i of sfs2d_plan_null_run uses
+ * (c = philox4x32((i >> 1, r, m, pool + 1), key); c.x | c.y << 32 for even i, c.z | c.w << 32 for odd i: the block
+ * length is not part of the counter); draw j = i * block + k (0 <= k < block, j < m) is SNP
+ * lo + (s_i + k) mod n.  The pool is circular (every SNP keeps its marginal probability; pool -1 is one circle
+ * over all chromosomes), the last block is cut at m, a block longer than the pool goes round it.  block == 1 is
+ * sfs2d_plan_null_run itself (the same kernel, byte-equal records); any block >= m is one run of m consecutive
+ * SNPs: a random placement of a window of m SNPs on the pool.  A record is a function of (seed, pool, m, block,
+ * r) alone.  Everything else -- tasks, pools, backgrounds, the record layout, out_dev, sfs2d_plan_null_read, the
+ * refusals and caps -- is sfs2d_plan_null_run's; in addition SFS2D_E_ARG for block < 1 or block >= 2^32. */
+int sfs2d_plan_null_run_blocks(sfs2d_plan* plan, const sfs2d_null_params* np, int64_t block, const int64_t* tasks,
+                               int64_t ntasks, sfs2d_window* out_dev);
 int sfs2d_plan_null_read(sfs2d_plan* plan, sfs2d_window* out_host, int64_t cap, int64_t* nrec_out);
 /* launch geometry (threads per grid) of k_prep and of the scan kernel: matches the Grid_Size column
  * of rocprofv3 kernel traces, so profiles can be joined to a plan */

@@ -10,7 +10,12 @@ their contents), the default size classes of the 20 kb scan's windows per pool, 
 Plan.null_run into a device buffer, host clock around the call and a stream synchronise -- beside the same
 plan's scan pass (run + synchronise, median).  Prints one JSON line.
 
-usage: python tools/null_bench.py [--reps 50] [--rounds 5] [--pools 32]"""
+--block B[,B...] (block lengths, "window" = one run per replicate window) adds the block null (kernel
+k_null_blk; block 1 is k_null) beside it: "kernel_blocks" -- the three single-task lines per block length,
+the variants alternated inside every round, median of the rounds -- and "genome_blocks", the whole-genome
+call at block 1 and at the last block length given, alternated.  Without it the output is unchanged.
+
+usage: python tools/null_bench.py [--reps 50] [--rounds 5] [--pools 32] [--block 1,8,64,window]"""
 import argparse
 import json
 import os
@@ -34,7 +39,13 @@ ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--pools", type=int, default=32)
 ap.add_argument("--snps", type=int, default=1_562_500)
+ap.add_argument("--block", default=None, metavar="B[,B...]")
 a = ap.parse_args()
+blocks = []   # (name, block length)
+for tok in (a.block.split(",") if a.block else []):
+    blocks.append((tok, 0xFFFFFFFF if tok == "window" else int(tok)))
+    if not 1 <= blocks[-1][1] <= 0xFFFFFFFF:
+        sys.exit(f"null_bench: block length {tok!r} not in [1, 2^32) or 'window'")
 if not torch.cuda.is_available():
     sys.exit("null_bench: no GPU (timings are taken on the device only)")
 
@@ -72,6 +83,20 @@ for m in (358, 16, 4096):
     med = statistics.median(ms)
     out["kernel"][str(m)] = {"ms": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
                              "draws_per_s": m * R / (med * 1e-3), "replicates": R}
+if blocks:   # the same lines per block length, alternated inside a round (block 1: k_null, the baseline)
+    out["kernel_blocks"] = {}
+    for m in (16, 358, 4096):
+        calls = {nm: (lambda b=b: pl.null_run([(0, m)], R, 1, out_dev_ptr=buf.data_ptr(), block=b)) for nm, b in blocks}
+        for c in calls.values():
+            c()
+        stream.synchronize()
+        ms = {nm: [] for nm in calls}
+        for _ in range(a.rounds):
+            for nm, c in calls.items():
+                ms[nm].append(event_ms(c, a.reps))
+        out["kernel_blocks"][str(m)] = {
+            nm: {"ms": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                 "draws_per_s": m * R / (statistics.median(v) * 1e-3), "replicates": R} for nm, v in ms.items()}
 pl.close()
 dev.close()
 del buf
@@ -112,6 +137,16 @@ out["genome"] = {"pools": k, "snps": g.n, "windows": int(len(recs)), "tasks": le
                  "scan_pass_ms_max": round(max(scan), 3),
                  "null_over_scan": statistics.median(null) / statistics.median(scan),
                  "draws_per_s": draws / (statistics.median(null) * 1e-3)}
+if blocks:   # the whole-genome call, single SNPs and the last block length given, alternated
+    pair = [("1", 1), blocks[-1]]
+    calls = {nm: (lambda b=b: pl.null_run(tasks, R, 1, out_dev_ptr=buf.data_ptr(), block=b)) for nm, b in pair}
+    ms = {nm: [wall_ms(c)][:0] for nm, c in calls.items()}   # (one untimed call each)
+    for _ in range(a.rounds):
+        for nm, c in calls.items():
+            ms[nm].append(wall_ms(c))
+    out["genome_blocks"] = {nm: {"null_ms": round(statistics.median(v), 3), "null_ms_min": round(min(v), 3),
+                                 "null_ms_max": round(max(v), 3), "draws_per_s": draws / (statistics.median(v) * 1e-3)}
+                            for nm, v in ms.items()}
 pl.close()
 dev.close()
 print(json.dumps(out))
