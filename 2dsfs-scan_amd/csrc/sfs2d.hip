@@ -132,6 +132,13 @@ struct sfs2d_data {
   // segmentation pass over the positions (the generator placed window w's SNPs in its own window)
   unsigned long long* d_win_off = nullptr;
   uint32_t win_bp = 0, win_per_chrom = 0;
+  // the position index (k_pos_index; data_pos_index builds it when the first plan that wants it is created,
+  // for a data set whose positions the library owns -- an upload, generated replicates; it serves plans of any
+  // window size and is freed with the data set): d_pidx the entries, d_pidx_base nchrom + 1 entry bases, d_pidx_sh nchrom cell shifts
+  mutable std::mutex pidx_mu;
+  mutable uint32_t* d_pidx = nullptr;
+  mutable uint32_t* d_pidx_base = nullptr;
+  mutable uint32_t* d_pidx_sh = nullptr;
 };
 
 struct sfs2d_plan {
@@ -143,6 +150,8 @@ struct sfs2d_plan {
   bool do_bg = false, do_seg = false, lds_hist = true, bg_ready = false;
   bool seg_synth = false;   // fixed-bp slots from the generator's window offsets (slots_only)
   bool seg_search = false;  // fixed-bp slots by binary search on the positions, k_slots_search (slots_only)
+  bool seg_index = false;   // fixed-bp slots from the data set's position index, k_slots_index ahead of a k_prep
+                            // that does not segment (counts plans with per-chromosome backgrounds)
   int64_t step = 0;         // sliding plan: fixed-bp windows advanced by step bp (0: disjoint windows); its
                             // slots by k_slots_slide, k_prep without segmentation
   bool fused = false;       // per-chromosome tables built inside k_scan_w (parity-alternating replicas)
@@ -448,6 +457,20 @@ hipError_t launch_slots_only(sfs2d_plan* pl) {
     hipExtLaunchKernelGGL(k_slots_search, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, CTX_STREAM(pl->ctx),
                           pl->kev[0], pl->kev[1], 0, pl->data->pos, pl->data->d_chrom_off, pl->d_slot_base,
                           pl->data->nchrom, (uint32_t)pl->prm.window, (uint32_t)nw, pl->d_slots);
+  return hipGetLastError();
+}
+
+// a seg_index plan's slot table, ahead of its k_prep.  The two kernels are the run's segmentation +
+// background stage: the stage's start event goes into this kernel's packet, its end event stays for
+// k_prep's (which then carries no start event)
+hipError_t launch_slots_index(sfs2d_plan* pl) {
+  const uint32_t ns = (uint32_t)pl->nslots;
+  if (!ns) return hipSuccess;
+  const sfs2d_data* d = pl->data;
+  hipExtLaunchKernelGGL(k_slots_index, dim3((ns + 255u) / 256u), dim3(256), 0, CTX_STREAM(pl->ctx), pl->kev[0], nullptr, 0,
+                        d->pos, d->d_chrom_off, pl->d_slot_base, d->d_pidx, d->d_pidx_base, d->d_pidx_sh, d->nchrom,
+                        (uint32_t)pl->prm.window, ns, pl->d_slots);
+  pl->kev[0] = nullptr;
   return hipGetLastError();
 }
 
@@ -839,7 +862,52 @@ int sfs2d_data_free(sfs2d_data* d) {
   if (d->owned || d->ann_owned) hipFree(d->ann);
   hipFree(d->d_chrom_off);
   hipFree(d->d_win_off);
+  hipFree(d->d_pidx); hipFree(d->d_pidx_base); hipFree(d->d_pidx_sh);
   delete d;
+  return 0;
+}
+
+// The data set's position index (k_pos_index), built on first use: 0.1 ms for 5e7 SNPs, <= 0.25 B/SNP plus
+// two words per chromosome.  A chromosome without SNPs has no entries.
+static int data_pos_index(sfs2d_ctx* ctx, const sfs2d_data* d) {
+  std::lock_guard<std::mutex> g(d->pidx_mu);
+  if (d->d_pidx) return 0;
+  const int nc = d->nchrom;
+  std::vector<uint32_t> base(nc + 1, 0), sh(std::max(1, nc), 0);
+  unsigned long long nent = 0;
+  for (int c = 0; c < nc; ++c) {
+    const int64_t len = d->chrom_off[c + 1] - d->chrom_off[c];
+    if (len > 0) {
+      const unsigned long long want = (unsigned long long)std::max<int64_t>(1, len / 16);
+      uint32_t s = 0;
+      while (((unsigned long long)d->last_pos[c] >> s) + 1ull > want) ++s;   // (s <= 32: one cell)
+      sh[c] = s;
+      nent += ((unsigned long long)d->last_pos[c] >> s) + 2ull;
+    }
+    base[c + 1] = (uint32_t)nent;
+  }
+  if (nent > 0xffffffffull) return set_err(ctx, SFS2D_E_ARG, "position index too large");
+  uint32_t *idx = nullptr, *db = nullptr, *ds = nullptr;
+  int rc = dalloc(ctx, &idx, (size_t)nent);
+  rc = rc ? rc : dalloc(ctx, &db, base.size());
+  rc = rc ? rc : dalloc(ctx, &ds, sh.size());
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    hipStream_t st = CTX_STREAM(ctx);
+    e = hipMemcpyAsync(db, base.data(), sizeof(uint32_t) * base.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ds, sh.data(), sizeof(uint32_t) * sh.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nent) {
+      hipLaunchKernelGGL(k_pos_index, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, d->pos, d->d_chrom_off, db, ds,
+                         nc, (uint32_t)nent, idx);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // (base and sh leave scope)
+  }
+  if (rc || e != hipSuccess) {
+    hipFree(idx); hipFree(db); hipFree(ds);
+    return rc ? rc : set_err(ctx, SFS2D_E_HIP, std::string("position index: ") + hipGetErrorString(e));
+  }
+  d->d_pidx = idx; d->d_pidx_base = db; d->d_pidx_sh = ds;
   return 0;
 }
 
@@ -957,7 +1025,8 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // Any other fixed-bp counts plan with a supplied background (no k_prep histograms) takes its slots by
   // binary search on the resident positions (k_slots_search) instead of k_prep's segmentation pass.
   // SFS2D_SEG=prep forces k_prep's segmentation, SFS2D_SEG=search the search (never the generator's
-  // offsets: what a real replicate VCF gets); both are selected by tests/test_synth_device.py
+  // offsets: what a real replicate VCF gets); both are selected by tests/test_synth_device.py.  SFS2D_SEG=index
+  // names what plans with per-chromosome backgrounds take unless it is prep (seg_index below, tests/test_slot_index.py)
   const char* seg_ev = std::getenv("SFS2D_SEG");
   const bool seg_prep = seg_ev && std::strcmp(seg_ev, "prep") == 0, seg_srch = seg_ev && std::strcmp(seg_ev, "search") == 0;
   if (bp && !slide && data->d_win_off && (uint32_t)prm->window == data->win_bp && pl->cnt && !pl->do_bg &&
@@ -966,10 +1035,12 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     for (int c = 0; c < nc && all; ++c) all = data->chrom_off[c + 1] > data->chrom_off[c];
     pl->seg_synth = all && !seg_prep && !seg_srch;
   }
-  // (Not with per-chromosome backgrounds, whose k_prep runs anyway: there a search before a counts-only
-  // k_prep cost more than the positions it saved k_prep -- config 3: k_prep 83.5 -> 64.5 us but one pass
-  // 0.214 -> 0.225 ms, the overlapped step 0.184 -> 0.191 ms, config 2 2.4e8 -> 2.0e8 windows/s; as extra
-  // blocks of k_prep itself, concurrent with its tiles: 0.185 -> 0.193 ms; profiles/r06e_*, r06f_*.)
+  // (Not with per-chromosome backgrounds, whose k_prep runs anyway: there this search -- ~21 dependent
+  // loads over ~6 lines per boundary -- before a counts-only k_prep cost more than the positions it saved
+  // k_prep: config 3: k_prep 83.5 -> 64.5 us but one pass 0.214 -> 0.225 ms, the overlapped step 0.184 ->
+  // 0.191 ms, config 2 2.4e8 -> 2.0e8 windows/s; as extra blocks of k_prep itself, concurrent with its
+  // tiles: 0.185 -> 0.193 ms; profiles/r06e_*, r06f_*.  Those plans take their slots from the data set's
+  // position index instead, seg_index below: one index read and a search inside one or two lines.)
   pl->seg_search = bp && !slide && pl->cnt && !pl->do_bg && !pl->seg_synth && !seg_prep;
   pl->K.nm1 = data->n > 0 ? (uint32_t)(data->n - 1) : 0u;
   pl->K.kmul = (uint32_t)(pl->K.n2 + 1) | (1u << 16);
@@ -1172,6 +1243,20 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // a sliding plan has no k_prep sums (they are per disjoint window): Fst where the scan does not sum it is
   // k_fst_win over the sliding slots, launched on its own before the scan
   if (slide) pl->fst_win = pl->fst && !pl->fst_scan;
+  // Fixed-bp counts plans with per-chromosome backgrounds whose k_prep has no per-window work (no Fst sums
+  // of its own): the slot table from the data set's position index (k_slots_index, ahead of k_prep on the
+  // plan's stream), and k_prep without segmentation -- it then reads no positions (4 B/SNP instead of 8)
+  // and has no window-id header, neighbour load or boundary branch.  SFS2D_SEG=prep: k_prep's
+  // segmentation.  (An attached plan takes its slots from k_slots_bp inside its base's run; its base qualifies.)
+  // Only for positions the library owns (an upload, generated replicates): a caller's wrapped device arrays may
+  // be written after the plan is created, in stream order ahead of a run (tests/test_stream_contract.py), or
+  // between runs, so no index built from them once holds; they keep k_prep's segmentation.
+  pl->seg_index = bp && !slide && pl->cnt && pl->do_bg && !seg_prep && force_sliced < 0 && data->owned &&
+                  !(pl->fst && !pl->fst_win && !pl->fst_scan);
+  if (pl->seg_index) {
+    if ((rc = data_pos_index(ctx, data))) { delete pl; return rc; }
+    pl->do_seg = false;
+  }
   pl->nfst = pl->fst_win && !slide ? (int)std::min<int64_t>(1024, std::max<int64_t>(1, (pl->nslots + 7) / 8)) : 0;   // ~1 window per wave
   if (pl->scan_lds > 64 * 1024) {
     const int lds = (int)pl->scan_lds;
@@ -1428,7 +1513,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   rc = rc ? rc : dalloc(ctx, &pl->d_err, 4);
   if (pl->fst) rc = rc ? rc : dalloc(ctx, &pl->d_fst, (size_t)pl->nslots + 1);
   pl->d_fst_own = pl->d_fst;
-  if ((pl->seg_search || slide) && !rc) {   // k_slots_search's / k_slots_slide's slot bases per chromosome (u32: nslots < 2^31)
+  if ((pl->seg_search || pl->seg_index || slide) && !rc) {   // k_slots_search's / k_slots_index's / k_slots_slide's slot bases per chromosome (u32: nslots < 2^31)
     std::vector<uint32_t> sb(pl->slot_base_h.begin(), pl->slot_base_h.end());
     rc = dalloc(ctx, &pl->d_slot_base, sb.size());
     if (!rc && hipMemcpy(pl->d_slot_base, sb.data(), sizeof(uint32_t) * sb.size(), hipMemcpyHostToDevice) != hipSuccess)
@@ -1519,6 +1604,7 @@ int sfs2d_plan_run_phase(sfs2d_plan* pl, int phase, sfs2d_window* out_dev) {
       HIPCHK(ctx, launch_slots_only(pl));
       if (pl->nslots == 0 && (rc = mark(0))) return rc;
     } else {
+      if (pl->seg_index) HIPCHK(ctx, launch_slots_index(pl));
       HIPCHK(ctx, launch_prep(pl, true));
       const bool slots = pl->step && pl->nslots;   // a sliding plan's table, after k_prep
       if (slots) HIPCHK(ctx, launch_slots_slide(pl, !prep_runs(pl)));
@@ -1553,6 +1639,15 @@ const char* sfs2d_plan_scan_kernel(const sfs2d_plan* pl) {
   if (!pl) return nullptr;
   if (pl->gw) return "k_scan_gw";
   return pl->G == WAVE ? "k_scan_w" : "k_scan_g";
+}
+
+const char* sfs2d_plan_seg_kind(const sfs2d_plan* pl) {
+  if (!pl) return nullptr;
+  if (pl->base) return pl->step ? "slide" : pl->prm.window_mode == SFS2D_WINDOW_BP ? "bp" : "none";
+  if (pl->step) return "slide";
+  if (pl->seg_index) return "index";
+  if (slots_only(pl)) return pl->seg_synth ? "synth" : "search";
+  return pl->do_seg ? "prep" : "none";
 }
 
 int sfs2d_plan_scan_variant(const sfs2d_plan* pl, int* p16, int* fused, int* fst, int* cnt, int* gate, int* tri) {
@@ -2099,6 +2194,7 @@ int sfs2d_plan_time(sfs2d_plan* pl, int iters, double* ms_run, double* ms_k1, do
   double t1 = 0, t2 = 0, t3 = 0, tall = 0;
   for (int it = 0; it < iters; ++it) {
     HIPCHK(ctx, hipEventRecord(pl->ev[0], st));
+    if (pl->seg_index) HIPCHK(ctx, launch_slots_index(pl));
     HIPCHK(ctx, slots_only(pl) ? launch_slots_only(pl) : launch_prep(pl, true));
     if (pl->step) HIPCHK(ctx, launch_slots_slide(pl, false));
     HIPCHK(ctx, hipEventRecord(pl->ev[1], st));

@@ -3507,6 +3507,69 @@ __global__ __launch_bounds__(256) void k_slots_search(const uint32_t* __restrict
   if (s < nslots) slots[s] = b < e ? make_uint2(b + 1u, e) : make_uint2(0u, 0u);
 }
 
+// The position index of a data set (built once, on the first plan that wants it; any window size): for
+// chromosome c, cells of 2^sh[c] bp, sh[c] the smallest shift that leaves at most max(1, len_c / 16) cells
+// (cells_c = (last_pos_c >> sh[c]) + 1 = ibase[c+1] - ibase[c] - 1).  Entry k of c (k = 0 .. cells_c, at
+// idx[ibase[c] + k]) is the global index of c's first SNP with pos >= (k << sh[c]) + 1; entry 0 is the
+// chromosome's first SNP (pos 0 lies in cell 0, as in window 0 for wid_of), entry cells_c its end.  One
+// thread per entry.  <= n / 16 + 2 nchrom words.
+__global__ __launch_bounds__(256) void k_pos_index(const uint32_t* __restrict__ pos, const long long* __restrict__ chrom_off,
+                                                   const uint32_t* __restrict__ ibase, const uint32_t* __restrict__ sh,
+                                                   int nchrom, uint32_t nent, uint32_t* __restrict__ idx) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= nent) return;
+  int lo = 0, hi = nchrom;   // chromosome c with ibase[c] <= e < ibase[c+1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ibase[mid] <= e) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t k = e - ibase[lo], cells = ibase[lo + 1] - ibase[lo] - 1u;
+  const uint32_t cb = (uint32_t)chrom_off[lo], ce = (uint32_t)chrom_off[lo + 1];
+  idx[e] = k == 0u ? cb : k >= cells ? ce : lower_bound_pos(pos, cb, ce, ((unsigned long long)k << sh[lo]) + 1ull);
+}
+
+// The slot table of a fixed-bp counts plan with per-chromosome backgrounds, from the data set's position
+// index (k_pos_index) instead of k_prep's segmentation pass over every position: window j's first SNP B_j
+// (the first with pos >= j ws + 1) lies in the index cell of j ws, so it is a search inside
+// [idx[k], idx[k+1]), k = (j ws) >> sh -- one index read and one or two lines of positions, whatever the
+// window size; past the chromosome's last cell it is the chromosome's end.  As k_slots_search: one thread
+// per slot, B_{j+1} from the next lane, the chromosome's end for its last window, every slot written every
+// run as (first + 1, last + 1) or (0, 0); bounds in 64 bits.
+__device__ __forceinline__ void slots_index(uint32_t s, const uint32_t* __restrict__ pos,
+                                            const long long* __restrict__ chrom_off, const uint32_t* __restrict__ slot_base,
+                                            const uint32_t* __restrict__ idx, const uint32_t* __restrict__ ibase,
+                                            const uint32_t* __restrict__ sh, int nchrom, uint32_t ws, uint32_t nslots,
+                                            uint2* __restrict__ slots) {
+  const uint32_t sc = min(s, nslots - 1u);   // (lanes past the end search too: their neighbours read them)
+  int lo = 0, hi = nchrom;                   // chromosome c with slot_base[c] <= sc < slot_base[c+1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (slot_base[mid] <= sc) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t j = sc - slot_base[lo], ns = slot_base[lo + 1] - slot_base[lo];
+  const uint32_t cb = (uint32_t)chrom_off[lo], ce = (uint32_t)chrom_off[lo + 1];
+  const uint32_t ib = ibase[lo], cells = ibase[lo + 1] - ib - 1u, shc = sh[lo];
+  auto bound = [&](uint32_t jj) -> uint32_t {   // the first SNP of the chromosome with pos >= jj ws + 1
+    const unsigned long long p = (unsigned long long)jj * ws, k = p >> shc;
+    if (k >= (unsigned long long)cells) return ce;
+    return lower_bound_pos(pos, idx[ib + (uint32_t)k], idx[ib + (uint32_t)k + 1u], p + 1ull);
+  };
+  const uint32_t b = j ? bound(j) : cb;
+  uint32_t e = __shfl_down(b, 1, WAVE);
+  if (j + 1u == ns) e = ce;
+  else if ((threadIdx.x & (WAVE - 1)) == WAVE - 1 || s + 1u >= nslots) e = bound(j + 1u);
+  if (s < nslots) slots[s] = b < e ? make_uint2(b + 1u, e) : make_uint2(0u, 0u);
+}
+
+__global__ __launch_bounds__(256) void k_slots_index(const uint32_t* __restrict__ pos, const long long* __restrict__ chrom_off,
+                                                     const uint32_t* __restrict__ slot_base, const uint32_t* __restrict__ idx,
+                                                     const uint32_t* __restrict__ ibase, const uint32_t* __restrict__ sh,
+                                                     int nchrom, uint32_t ws, uint32_t nslots, uint2* __restrict__ slots) {
+  slots_index(blockIdx.x * 256u + threadIdx.x, pos, chrom_off, slot_base, idx, ibase, sh, nchrom, ws, nslots, slots);
+}
+
 // The slot table of a sliding plan (sfs2d_plan_create_sliding / _attach_sliding): windows of ws bp
 // advanced by `step` bp (ws % step == 0).  Slot j of chromosome c holds the SNPs with
 // j step + 1 <= pos <= j step + ws: begin = the first SNP with pos >= j step + 1 (slot 0: the

@@ -354,6 +354,11 @@ class Plan:
         """Name of the scan kernel this plan launches (the prefix of its rocprofv3 kernel name)."""
         return self.eng.lib.sfs2d_plan_scan_kernel(self.h).decode()
 
+    def seg_kind(self) -> str:
+        """Where this plan's window slots come from (sfs2d_plan_seg_kind): "prep", "index", "search", "synth",
+        "slide", "bp" or "none"."""
+        return self.eng.lib.sfs2d_plan_seg_kind(self.h).decode()
+
     def scan_variant(self) -> dict:
         """Template arguments of the scan kernel this plan's last run launched (sfs2d_plan_scan_variant):
         {"p16", "fused", "fst", "cnt", "gate", "tri"}, -1 where the kernel has no such argument; raises

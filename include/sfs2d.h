@@ -133,6 +133,12 @@ int sfs2d_data_upload(sfs2d_ctx* ctx, const uint32_t* counts, const uint32_t* po
 int sfs2d_data_wrap_device(sfs2d_ctx* ctx, const uint32_t* d_counts, const uint32_t* d_pos,
                            const uint16_t* d_ann_id, int64_t n, const int64_t* chrom_off,
                            const uint32_t* chrom_last_pos, int32_t nchrom, sfs2d_data** out);
+/* A data set whose positions the library owns (sfs2d_data_upload, sfs2d_data_synth_sims) also owns a position
+ * index, built on the device (0.1 ms for 5e7 SNPs) when the first plan that takes its window slots from it is
+ * created (sfs2d_plan_seg_kind "index"); it serves plans of any window size and is freed here, so the data set
+ * must outlive its plans as before.  Device memory: at most 0.25 B/SNP plus a few words per chromosome.
+ * Wrapped device arrays (sfs2d_data_wrap_device) get none: their contents are the caller's and may be written
+ * after a plan is created, in stream order ahead of a run; their plans read the positions on every pass. */
 int sfs2d_data_free(sfs2d_data* data);
 
 /* Synthetic sims replicates generated in HBM (BASELINE config 4: sims_scan.likelihood_scan's
@@ -311,6 +317,13 @@ int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* sca
 /* name of the scan kernel the plan launches ("k_scan_w", "k_scan_gw", "k_scan_g"; the
  * prefix of its rocprofv3 kernel name), NULL for a null plan */
 const char* sfs2d_plan_scan_kernel(const sfs2d_plan* plan);
+/* where the plan's window slots come from: "prep" (k_prep's segmentation pass over the positions), "index"
+ * (k_slots_index over the data set's position index, ahead of a k_prep that reads no positions: fixed-bp
+ * counts plans with per-chromosome backgrounds over uploaded or generated data, unless SFS2D_SEG=prep at plan
+ * creation), "search"
+ * (k_slots_search), "synth" (the generator's window offsets), "slide" (k_slots_slide), "bp" (an attached
+ * fixed-bp plan: k_slots_bp), "none" (SNP-count windows); NULL for a null plan */
+const char* sfs2d_plan_seg_kind(const sfs2d_plan* plan);
 /* template arguments of the scan kernel the plan's last run launched; -1 where the kernel has no such argument
  * (k_scan_w: p16, fused, fst 0..3, cnt, gate; k_scan_gw: p16, fst, cnt, tri; k_scan_g: p16, fst, cnt).  p16 == 0:
  * 32-bit 2D bins in LDS (a window may hold >= 65,536 SNPs).  An attached plan records at its own launch inside
