@@ -152,6 +152,10 @@ struct sfs2d_plan {
   bool seg_search = false;  // fixed-bp slots by binary search on the positions, k_slots_search (slots_only)
   bool seg_index = false;   // fixed-bp slots from the data set's position index, k_slots_index ahead of a k_prep
                             // that does not segment (counts plans with per-chromosome backgrounds)
+  // seg_index plans whose scan never stores to the slot table (Fst summed in the scan): the table depends on
+  // the position index, the window and the slot bases alone, all fixed for the plan, so the plan's first run
+  // writes it and later runs launch no slot kernel (stage_slots)
+  bool slots_once = false, slots_written = false;
   int64_t step = 0;         // sliding plan: fixed-bp windows advanced by step bp (0: disjoint windows); its
                             // slots by k_slots_slide, k_prep without segmentation
   bool fused = false;       // per-chromosome tables built inside k_scan_w (parity-alternating replicas)
@@ -472,6 +476,25 @@ hipError_t launch_slots_index(sfs2d_plan* pl) {
                         (uint32_t)pl->prm.window, ns, pl->d_slots);
   pl->kev[0] = nullptr;
   return hipGetLastError();
+}
+
+// a seg_index plan's slot table for the run being enqueued.  slots_once plans: k_slots_index in the plan's first
+// run alone -- afterwards the stage is k_prep alone, whose packet then carries the stage's start event as well,
+// and a pass has one launch and one ~14 us chain of dependent loads less (config 3).  The plan's later runs
+// come after its first in stream order, or in an order the caller makes, as its per-run state asks anyway.
+// Under stream capture the kernel is launched as ever and nothing is marked: a captured launch writes nothing
+// before a replay.
+hipError_t stage_slots(sfs2d_plan* pl) {
+  if (!pl->slots_once) return launch_slots_index(pl);
+  if (pl->slots_written) return hipSuccess;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(CTX_STREAM(pl->ctx), &cs) != hipSuccess) {   // (e.g. the null stream while another stream captures)
+    (void)hipGetLastError();
+    return launch_slots_index(pl);
+  }
+  const hipError_t e = launch_slots_index(pl);
+  if (e == hipSuccess && cs == hipStreamCaptureStatusNone) pl->slots_written = true;
+  return e;
 }
 
 // whether a plan run launches k_prep at all
@@ -1257,6 +1280,10 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     if ((rc = data_pos_index(ctx, data))) { delete pl; return rc; }
     pl->do_seg = false;
   }
+  // ... and with Fst summed in the scan no kernel but k_slots_index stores to the table (the scan's slot clear
+  // is the Fst-free variants'): it is written once per plan.  SFS2D_SLOTS_ONCE=0: every run, for comparison
+  pl->slots_once = pl->seg_index && pl->fst_scan;
+  if (const char* ev = std::getenv("SFS2D_SLOTS_ONCE")) pl->slots_once = pl->slots_once && ev[0] != '0';
   pl->nfst = pl->fst_win && !slide ? (int)std::min<int64_t>(1024, std::max<int64_t>(1, (pl->nslots + 7) / 8)) : 0;   // ~1 window per wave
   if (pl->scan_lds > 64 * 1024) {
     const int lds = (int)pl->scan_lds;
@@ -1604,7 +1631,7 @@ int sfs2d_plan_run_phase(sfs2d_plan* pl, int phase, sfs2d_window* out_dev) {
       HIPCHK(ctx, launch_slots_only(pl));
       if (pl->nslots == 0 && (rc = mark(0))) return rc;
     } else {
-      if (pl->seg_index) HIPCHK(ctx, launch_slots_index(pl));
+      if (pl->seg_index) HIPCHK(ctx, stage_slots(pl));
       HIPCHK(ctx, launch_prep(pl, true));
       const bool slots = pl->step && pl->nslots;   // a sliding plan's table, after k_prep
       if (slots) HIPCHK(ctx, launch_slots_slide(pl, !prep_runs(pl)));
@@ -1649,6 +1676,8 @@ const char* sfs2d_plan_seg_kind(const sfs2d_plan* pl) {
   if (slots_only(pl)) return pl->seg_synth ? "synth" : "search";
   return pl->do_seg ? "prep" : "none";
 }
+
+int sfs2d_plan_slots_once(const sfs2d_plan* pl) { return !pl ? SFS2D_E_ARG : pl->slots_once ? 1 : 0; }
 
 int sfs2d_plan_scan_variant(const sfs2d_plan* pl, int* p16, int* fused, int* fst, int* cnt, int* gate, int* tri) {
   if (!pl) return SFS2D_E_ARG;
@@ -1820,7 +1849,15 @@ int sfs2d_graph_create(sfs2d_plan* const* plans, void* const* streams, sfs2d_win
   hipStream_t saved = CTX_STREAM(ctx);
   int rc = 0;
   hipError_t e = hipSuccess;
+  // a slots_once plan that has not run yet writes its slot table now, on its stream and ahead of the capture
+  // (synchronised below): the graphs then hold no slot kernel
+  for (int k = 0; k < nplans && k < nruns && e == hipSuccess; ++k)
+    if (plans[k]->seg_index && plans[k]->slots_once && !plans[k]->slots_written) {
+      ctx->stream = (hipStream_t)streams[k];
+      e = stage_slots(plans[k]);
+    }
   for (hipStream_t s : g->streams) {
+    if (e != hipSuccess) break;
     // run i of the sequence is plan i % nplans on its stream: this stream's chain, in sequence order
     e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
@@ -2194,7 +2231,7 @@ int sfs2d_plan_time(sfs2d_plan* pl, int iters, double* ms_run, double* ms_k1, do
   double t1 = 0, t2 = 0, t3 = 0, tall = 0;
   for (int it = 0; it < iters; ++it) {
     HIPCHK(ctx, hipEventRecord(pl->ev[0], st));
-    if (pl->seg_index) HIPCHK(ctx, launch_slots_index(pl));
+    if (pl->seg_index) HIPCHK(ctx, stage_slots(pl));
     HIPCHK(ctx, slots_only(pl) ? launch_slots_only(pl) : launch_prep(pl, true));
     if (pl->step) HIPCHK(ctx, launch_slots_slide(pl, false));
     HIPCHK(ctx, hipEventRecord(pl->ev[1], st));

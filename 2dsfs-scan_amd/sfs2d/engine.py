@@ -359,6 +359,10 @@ class Plan:
         "slide", "bp" or "none"."""
         return self.eng.lib.sfs2d_plan_seg_kind(self.h).decode()
 
+    def slots_once(self) -> bool:
+        """Whether the slot table is written by the plan's first run alone (sfs2d_plan_slots_once)."""
+        return self.eng.lib.sfs2d_plan_slots_once(self.h) == 1
+
     def scan_variant(self) -> dict:
         """Template arguments of the scan kernel this plan's last run launched (sfs2d_plan_scan_variant):
         {"p16", "fused", "fst", "cnt", "gate", "tri"}, -1 where the kernel has no such argument; raises

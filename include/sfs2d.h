@@ -324,6 +324,11 @@ const char* sfs2d_plan_scan_kernel(const sfs2d_plan* plan);
  * (k_slots_search), "synth" (the generator's window offsets), "slide" (k_slots_slide), "bp" (an attached
  * fixed-bp plan: k_slots_bp), "none" (SNP-count windows); NULL for a null plan */
 const char* sfs2d_plan_seg_kind(const sfs2d_plan* plan);
+/* 1: the plan's slot table is written by its first run alone and later runs launch no slot kernel -- "index"
+ * plans with Fst summed in the scan, whose scan never stores to the table (its inputs, the data set's position
+ * index, the window and the slot bases, are fixed for the plan); 0: every run writes it (also with
+ * SFS2D_SLOTS_ONCE=0 at plan creation); SFS2D_E_ARG for a null plan */
+int sfs2d_plan_slots_once(const sfs2d_plan* plan);
 /* template arguments of the scan kernel the plan's last run launched; -1 where the kernel has no such argument
  * (k_scan_w: p16, fused, fst 0..3, cnt, gate; k_scan_gw: p16, fst, cnt, tri; k_scan_g: p16, fst, cnt).  p16 == 0:
  * 32-bit 2D bins in LDS (a window may hold >= 65,536 SNPs).  An attached plan records at its own launch inside
