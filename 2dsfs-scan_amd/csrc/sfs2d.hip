@@ -16,6 +16,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -23,6 +24,7 @@
 #include <cstring>
 #include <string>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "sfs2d.h"
@@ -236,8 +238,8 @@ struct sfs2d_plan {
   size_t null_cap = 0;
   const sfs2d_window* null_last = nullptr;   // where the last call wrote (sfs2d_plan_null_read copies from it)
   int64_t null_nrec = 0;
-  // template arguments of the scan kernel the last run launched (sfs2d_plan_scan_variant), written by the
-  // launch_scan_* templates themselves: {P16, FUSED, FST, CNT, GATE, TRI}, -1 where the kernel has none
+  // template arguments of the scan kernel the last run launched (sfs2d_plan_scan_variant), written by
+  // launch_scan from the selection it launches: {P16, FUSED, FST, CNT, GATE, TRI}, -1 where the kernel has none
   int variant[6] = {-1, -1, -1, -1, -1, -1};
   bool variant_set = false;
   uint64_t null_tab_runs = ~0ull;        // fused / sliced plans: the run whose tables of EVERY chromosome are in
@@ -301,154 +303,237 @@ int repl_par(const sfs2d_plan* pl) { return pl->fused ? plan_par(pl) : 0; }
 // what the scan kernels stream per SNP: the bins k_prep wrote, or (counts plans) the counts themselves
 const uint32_t* scan_src(const sfs2d_plan* pl) { return pl->cnt ? pl->data->counts : pl->d_bins; }
 
+// -------------------------------------------------------------------------- kernel variants
+// Each templated kernel family has one struct of its template arguments (a selection), which names the
+// family's legal instantiations (legal) and numbers them (index / at); one table, variants<S>, holds the
+// kernel of every legal selection at its index and null elsewhere.  Launches, occupancy and static-LDS
+// queries and the dynamic-LDS limits all take their kernels from it, and one function per family
+// (scan_w_sel, ..., prep_sel) is the only place that turns plan flags into template arguments.  The
+// selections are made at launch (plan_attach rewrites fst_win after plan_create): a few branches and an
+// indexed load.
+
+// k_prep sums Fst per window slot (fixed point, d_fsum) and the scan takes the sums: Fst is asked for, and
+// neither window kernels (fst_win) nor the scan itself (fst_scan) compute it
+bool prep_sums_fst(const sfs2d_plan* pl) { return pl->fst && !pl->fst_win && !pl->fst_scan; }
+
+struct ScanW {   // k_scan_w<P16, FUSED, FST, CNT, GATE, LEAN>
+  bool p16, fused;
+  int fst;   // 0 none, 1 k_prep's sums, 2 summed in the scan, 3 the same with SNPs of < 2 called alleles dropped
+  bool cnt, gate, lean;
+  using Fn = void (*)(SCAN_W_ARGS);
+  static constexpr int N = 128;
+  constexpr int index() const { return p16 | fused << 1 | fst << 2 | cnt << 4 | gate << 5 | lean << 6; }
+  static constexpr ScanW at(int i) { return {bool(i & 1), bool(i & 2), (i >> 2) & 3, bool(i & 16), bool(i & 32), bool(i & 64)}; }
+  // Fst in the scan is a counts plan's; GATE and LEAN (a gated variant) are built for it alone
+  constexpr bool legal() const { return fst < 2 ? !gate && !lean : cnt && (gate || !lean); }
+  template <int I> static constexpr Fn kernel() { constexpr ScanW s = at(I); return k_scan_w<s.p16, s.fused, s.fst, s.cnt, s.gate, s.lean>; }
+};
+
+struct ScanGW {   // k_scan_gw<P16, FST, CNT, TRI>
+  bool p16, fst, cnt, tri;
+  using Fn = void (*)(SCAN_W_ARGS);
+  static constexpr int N = 16;
+  constexpr int index() const { return p16 | fst << 1 | cnt << 2 | tri << 3; }
+  static constexpr ScanGW at(int i) { return {bool(i & 1), bool(i & 2), bool(i & 4), bool(i & 8)}; }
+  constexpr bool legal() const { return cnt || !tri; }   // the triangle is a counts plan's
+  template <int I> static constexpr Fn kernel() { constexpr ScanGW s = at(I); return k_scan_gw<s.p16, s.fst, s.cnt, s.tri>; }
+};
+
+struct ScanG {   // k_scan_g<P16, FST, CNT>
+  bool p16, fst, cnt;
+  using Fn = decltype(&k_scan_g<true, true, true>);
+  static constexpr int N = 8;
+  constexpr int index() const { return p16 | fst << 1 | cnt << 2; }
+  static constexpr ScanG at(int i) { return {bool(i & 1), bool(i & 2), bool(i & 4)}; }
+  constexpr bool legal() const { return true; }
+  template <int I> static constexpr Fn kernel() { constexpr ScanG s = at(I); return k_scan_g<s.p16, s.fst, s.cnt>; }
+};
+
+struct ScanExtra {   // k_scan_extra<P16, CNT>
+  bool p16, cnt;
+  using Fn = decltype(&k_scan_extra<true, true>);
+  static constexpr int N = 4;
+  constexpr int index() const { return p16 | cnt << 1; }
+  static constexpr ScanExtra at(int i) { return {bool(i & 1), bool(i & 2)}; }
+  constexpr bool legal() const { return true; }
+  template <int I> static constexpr Fn kernel() { constexpr ScanExtra s = at(I); return k_scan_extra<s.p16, s.cnt>; }
+};
+
+struct Prep {   // k_prep<DO_BG, DO_SEG, LDS_HIST, DO_BINS, FILT, FST, JNT>
+  bool bg, seg, lds, bins, filt, fst, jnt;
+  using Fn = decltype(&k_prep<true, true, true, true, false, false>);
+  static constexpr int N = 128;
+  constexpr int index() const { return bg | seg << 1 | lds << 2 | bins << 3 | filt << 4 | fst << 5 | jnt << 6; }
+  static constexpr Prep at(int i) { return {bool(i & 1), bool(i & 2), bool(i & 4), bool(i & 8), bool(i & 16), bool(i & 32), bool(i & 64)}; }
+  constexpr bool legal() const {
+    if (lds && !bg) return false;   // the LDS histogram is the background's
+    if (jnt && !(lds && !bins && !filt && !fst)) return false;   // the joint histogram: a pass that only histograms and segments
+    // a pass without bins is a counts plan's, which has no filter, or sfs2d_bg_hist's, which only histograms
+    if (!bins && filt && !(bg && !seg && !fst)) return false;
+    return bg || seg || bins || fst;   // (a pass with nothing to do is not launched: prep_runs)
+  }
+  template <int I> static constexpr Fn kernel() { constexpr Prep s = at(I); return k_prep<s.bg, s.seg, s.lds, s.bins, s.filt, s.fst, s.jnt>; }
+};
+
+// entry I of family S's table: its kernel, instantiated only where the selection is legal
+template <class S, int I>
+constexpr typename S::Fn variant_at() {
+  if constexpr (S::at(I).legal()) return S::template kernel<I>();
+  else return nullptr;
+}
+template <class S, int... I>
+constexpr std::array<typename S::Fn, sizeof...(I)> variant_table(std::integer_sequence<int, I...>) {
+  return {{variant_at<S, I>()...}};
+}
+template <class S>
+constexpr std::array<typename S::Fn, S::N> variants = variant_table<S>(std::make_integer_sequence<int, S::N>{});
+
+// the kernel of a selection, null with SFS2D_E_ARG in *rc when it is outside its family's table
+template <class S>
+typename S::Fn variant(sfs2d_ctx* ctx, S s, const char* family, int* rc) {
+  const typename S::Fn k = variants<S>[s.index()];
+  *rc = k ? 0 : set_err(ctx, SFS2D_E_ARG, std::string(family) + ": the plan selects an instantiation outside the kernel table");
+  return k;
+}
+
+// the dynamic-LDS limit on every instantiation of a family (the first error, if any)
+template <class S>
+hipError_t set_max_lds(size_t lds) {
+  hipError_t e = hipSuccess;
+  for (const typename S::Fn k : variants<S>) {
+    if (!k) continue;
+    const hipError_t ek = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = ek;
+  }
+  return e;
+}
+
+// a selection's static LDS (fallback: the query failed) and its resident workgroups per CU (0: it failed)
+template <class S>
+size_t static_lds(S s, size_t fallback) {
+  hipFuncAttributes fa{};
+  return hipFuncGetAttributes(&fa, (const void*)variants<S>[s.index()]) == hipSuccess ? fa.sharedSizeBytes : fallback;
+}
+template <class S>
+int occupancy(S s, int block, size_t lds) {
+  int occ = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, variants<S>[s.index()], block, lds) == hipSuccess ? occ : 0;
+}
+
+ScanW scan_w_sel(const sfs2d_plan* pl) {
+  const bool in_scan = pl->cnt && pl->fst_scan;
+  const int fst = in_scan ? (pl->fst_mask ? 3 : 2) : prep_sums_fst(pl) ? 1 : 0;
+  // (gate: no SNP's key can leave the inner grid, the variants without the range test; lean: gated, and the
+  // window loop's tail specialised for fixed-bp slots and n1p, n2p <= 31)
+  return {pl->p16, pl->fused, fst, pl->cnt, in_scan && (pl->gate || pl->lean), in_scan && pl->lean};
+}
+// (large grids: Fst from k_prep's sums, taken by the scan -- unless window kernels wrote it, fst_win)
+ScanGW scan_gw_sel(const sfs2d_plan* pl) { return {pl->p16, prep_sums_fst(pl), pl->cnt, pl->cnt && pl->K.ntri}; }
+ScanG scan_g_sel(const sfs2d_plan* pl) { return {pl->p16, prep_sums_fst(pl), pl->cnt}; }
+ScanExtra scan_extra_sel(const sfs2d_plan* pl) { return {pl->p16, pl->cnt}; }
+
+// The scan grid is one dispatch wave of resident workgroups, sized by the occupancy of a stand-in for the
+// variant that runs: Fst in the scan asked as FST 2, everything else as FST 1, and always as a counts plan.
+// Every k_scan_w / k_scan_gw variant is in one VGPR bucket under amdgpu_waves_per_eu(4), but the Fst-free
+// variants hold 512 B less static LDS, so a plan without Fst whose dynamic LDS lies within 512 B of the
+// boundary between one and two workgroups per CU would get another grid from its own variant.  Asking about
+// the variant itself is a change of behaviour, to be made with a measurement.
+ScanW occ_standin(ScanW s) { s.fst = s.fst >= 2 ? 2 : 1; s.cnt = true; return s; }
+ScanGW occ_standin(ScanGW s) { s.fst = s.cnt = true; return s; }
+
+// the instantiations whose static LDS plan_create counts: the small-grid path's fit test, Fst in the scan,
+// and k_prep's LDS histogram with and without its Fst sums
+constexpr ScanW SCAN_W_FIT = {true, true, 1, true, false, false};
+constexpr ScanW scan_w_fst_fit(bool p16) { return {p16, true, 2, true, false, false}; }
+constexpr Prep prep_lds_fit(bool fst) { return {true, true, true, true, false, fst, false}; }
+
+// template arguments of the scan kernel being launched: {P16, FUSED, FST, CNT, GATE, TRI}, -1 where it has none
 void set_variant(sfs2d_plan* pl, int p16, int fused, int fst, int cnt, int gate, int tri) {
   const int v[6] = {p16, fused, fst, cnt, gate, tri};
   std::copy(v, v + 6, pl->variant);
   pl->variant_set = true;
 }
 
-template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false, bool LEAN = false>
-void launch_scan_w(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
-  set_variant(pl, P16, FUSED, FST, CNT, GATE, -1);   // (LEAN: a gated variant, gate = 1)
-  hipExtLaunchKernelGGL((k_scan_w<P16, FUSED, FST, CNT, GATE, LEAN>), dim3((unsigned)pl->chunks.size()), dim3(SBLOCK), pl->scan_lds,
-                     CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_lp, pl->d_head,
-                     per_chrom, pl->ctx->d_lnx, pl->ctx->d_df, out, pl->d_err, bp, pl->d_repl, pl->d_bcount,
-                     plan_par(pl), pl->d_leaves, pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels,
-                     pl->extra_rec >= 0 ? (int)pl->last_chrom : -1, pl->d_fsum, pl->d_fst, pl->d_ctr,
-                     (int)(pl->runs & 1), pl->d_leafsum, pl->d_bg1d, pl->sliced ? 1 : 0, nullptr, 0);
-}
-
-template <bool P16, bool FST, bool CNT>
-void launch_scan_g(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
-  set_variant(pl, P16, -1, FST, CNT, -1, -1);
-  hipExtLaunchKernelGGL((k_scan_g<P16, FST, CNT>), dim3((unsigned)pl->chunks.size()), dim3(BLOCK), pl->scan_lds,
-                     CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_head, per_chrom,
-                     pl->ctx->d_lnx, out, bp, pl->d_fsum, pl->d_fst);
-}
-
-template <bool P16, bool FST, bool CNT, bool TRI = false>
-void launch_scan_gw(sfs2d_plan* pl, sfs2d_window* out, int per_chrom, int bp) {
-  set_variant(pl, P16, -1, FST, CNT, -1, TRI);
-  hipExtLaunchKernelGGL((k_scan_gw<P16, FST, CNT, TRI>), dim3((unsigned)pl->chunks.size()), dim3(WAVE), pl->scan_lds,
-                     CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_lp, pl->d_head,
-                     per_chrom, pl->ctx->d_lnx, pl->ctx->d_df, out, pl->d_err, bp, pl->d_repl, pl->d_bcount,
-                     0, pl->d_leaves, pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels, -1, pl->d_fsum, pl->d_fst,
-                     pl->d_ctr, (int)(pl->runs & 1), pl->d_leafsum, pl->d_bg1d, 0, pl->d_gscr, pl->nscr);
-}
-
-template <bool P16, bool CNT>
-hipError_t launch_scan_c(sfs2d_plan* pl, sfs2d_window* out) {
+int launch_scan(sfs2d_plan* pl, sfs2d_window* out) {
   const int per_chrom = pl->prm.bg_mode == SFS2D_BG_PER_CHROM ? 1 : 0;
   const int bp = pl->prm.window_mode == SFS2D_WINDOW_BP ? 1 : 0;
-  // (large grids: Fst from k_prep's sums, taken by the scan -- unless window kernels wrote it, fst_win)
-  const bool gfst = pl->fst && !pl->fst_win;
+  const dim3 grid((unsigned)pl->chunks.size());
+  int rc = 0;
   if (pl->gw) {
-    if (CNT && pl->K.ntri) {
-      if (gfst) launch_scan_gw<P16, true, CNT, CNT>(pl, out, per_chrom, bp);
-      else launch_scan_gw<P16, false, CNT, CNT>(pl, out, per_chrom, bp);
-    } else if (gfst) {
-      launch_scan_gw<P16, true, CNT>(pl, out, per_chrom, bp);
-    } else {
-      launch_scan_gw<P16, false, CNT>(pl, out, per_chrom, bp);
-    }
+    const ScanGW s = scan_gw_sel(pl);
+    const ScanGW::Fn k = variant(pl->ctx, s, "k_scan_gw", &rc);
+    if (!k) return rc;
+    set_variant(pl, s.p16, -1, s.fst, s.cnt, -1, s.tri);
+    hipExtLaunchKernelGGL(k, grid, dim3(WAVE), pl->scan_lds,
+                       CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_lp, pl->d_head,
+                       per_chrom, pl->ctx->d_lnx, pl->ctx->d_df, out, pl->d_err, bp, pl->d_repl, pl->d_bcount,
+                       0, pl->d_leaves, pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels, -1, pl->d_fsum, pl->d_fst,
+                       pl->d_ctr, (int)(pl->runs & 1), pl->d_leafsum, pl->d_bg1d, 0, pl->d_gscr, pl->nscr);
   } else if (pl->G == WAVE) {
-    if constexpr (CNT) {
-      if (pl->fst_scan) {
-        if (pl->lean) {   // (gated, and the window loop's tail specialised for fixed-bp slots and n1p, n2p <= 31)
-          if (pl->fst_mask) {
-            if (pl->fused) launch_scan_w<P16, true, 3, CNT, true, true>(pl, out, per_chrom, bp);
-            else launch_scan_w<P16, false, 3, CNT, true, true>(pl, out, per_chrom, bp);
-          } else {
-            if (pl->fused) launch_scan_w<P16, true, 2, CNT, true, true>(pl, out, per_chrom, bp);
-            else launch_scan_w<P16, false, 2, CNT, true, true>(pl, out, per_chrom, bp);
-          }
-        } else if (pl->gate) {   // (no SNP's key can leave the inner grid: the variants without the range test)
-          if (pl->fst_mask) {
-            if (pl->fused) launch_scan_w<P16, true, 3, CNT, true>(pl, out, per_chrom, bp);
-            else launch_scan_w<P16, false, 3, CNT, true>(pl, out, per_chrom, bp);
-          } else {
-            if (pl->fused) launch_scan_w<P16, true, 2, CNT, true>(pl, out, per_chrom, bp);
-            else launch_scan_w<P16, false, 2, CNT, true>(pl, out, per_chrom, bp);
-          }
-        } else if (pl->fst_mask) {
-          if (pl->fused) launch_scan_w<P16, true, 3, CNT>(pl, out, per_chrom, bp);
-          else launch_scan_w<P16, false, 3, CNT>(pl, out, per_chrom, bp);
-        } else {
-          if (pl->fused) launch_scan_w<P16, true, 2, CNT>(pl, out, per_chrom, bp);
-          else launch_scan_w<P16, false, 2, CNT>(pl, out, per_chrom, bp);
-        }
-        return hipGetLastError();
-      }
-    }
-    if (pl->fused) {
-      if (pl->fst && !pl->fst_win) launch_scan_w<P16, true, true, CNT>(pl, out, per_chrom, bp);
-      else launch_scan_w<P16, true, false, CNT>(pl, out, per_chrom, bp);
-    } else {
-      if (pl->fst && !pl->fst_win) launch_scan_w<P16, false, true, CNT>(pl, out, per_chrom, bp);
-      else launch_scan_w<P16, false, false, CNT>(pl, out, per_chrom, bp);
-    }
+    const ScanW s = scan_w_sel(pl);
+    const ScanW::Fn k = variant(pl->ctx, s, "k_scan_w", &rc);
+    if (!k) return rc;
+    set_variant(pl, s.p16, s.fused, s.fst, s.cnt, s.gate, -1);   // (LEAN: a gated variant, gate = 1)
+    hipExtLaunchKernelGGL(k, grid, dim3(SBLOCK), pl->scan_lds,
+                       CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_lp, pl->d_head,
+                       per_chrom, pl->ctx->d_lnx, pl->ctx->d_df, out, pl->d_err, bp, pl->d_repl, pl->d_bcount,
+                       plan_par(pl), pl->d_leaves, pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels,
+                       pl->extra_rec >= 0 ? (int)pl->last_chrom : -1, pl->d_fsum, pl->d_fst, pl->d_ctr,
+                       (int)(pl->runs & 1), pl->d_leafsum, pl->d_bg1d, pl->sliced ? 1 : 0, nullptr, 0);
   } else {
-    if (gfst) launch_scan_g<P16, true, CNT>(pl, out, per_chrom, bp);
-    else launch_scan_g<P16, false, CNT>(pl, out, per_chrom, bp);
+    const ScanG s = scan_g_sel(pl);
+    const ScanG::Fn k = variant(pl->ctx, s, "k_scan_g", &rc);
+    if (!k) return rc;
+    set_variant(pl, s.p16, -1, s.fst, s.cnt, -1, -1);
+    hipExtLaunchKernelGGL(k, grid, dim3(BLOCK), pl->scan_lds,
+                       CTX_STREAM(pl->ctx), pl->kev[4], pl->kev[5], 0, pl->K, scan_src(pl), pl->d_chunks, pl->d_slots, pl->d_tab, pl->d_head, per_chrom,
+                       pl->ctx->d_lnx, out, bp, pl->d_fsum, pl->d_fst);
   }
-  return hipGetLastError();
+  HIPCHK(pl->ctx, hipGetLastError());
+  return 0;
 }
 
-template <bool P16>
-hipError_t launch_scan(sfs2d_plan* pl, sfs2d_window* out) {
-  return pl->cnt ? launch_scan_c<P16, true>(pl, out) : launch_scan_c<P16, false>(pl, out);
+// whether a plan run launches k_prep at all: a counts plan's pass stores no bins, and is skipped when it has
+// nothing to do (supplied background, no segmentation of its own, no Fst sums)
+bool prep_runs(const sfs2d_plan* pl) {
+  return !pl->tiles.empty() && (!pl->cnt || pl->do_bg || pl->do_seg || prep_sums_fst(pl));
 }
 
-template <bool B, bool S, bool L, bool N, bool F, bool FS>
-hipError_t launch_prep3(sfs2d_plan* pl) {
-  const sfs2d_data* d = pl->data;
-  const int par = plan_par(pl);
-  auto go = [&](auto kern) {
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)pl->tiles.size()), dim3(BLOCK1),
-                       (B && L) ? pl->bg_lds : 0, CTX_STREAM(pl->ctx), pl->kev[0], pl->kev[1], 0, pl->K, d->counts, d->pos, d->ann, pl->d_tiles,
-                       pl->d_repl + (size_t)repl_par(pl) * REPL * pl->K.nchrom * pl->K.nh, pl->d_slots, pl->d_bins,
-                       pl->d_bcount + (size_t)par * pl->K.nchrom, pl->d_err, L ? pl->hr : 1,
-                       reinterpret_cast<const double2*>(pl->ctx->d_df + 2 * LNT), pl->d_fsum);
-    return hipGetLastError();
-  };
+// bins: a plan's pass; else the histogram-only pass of sfs2d_bg_hist
+Prep prep_sel(const sfs2d_plan* pl, bool bins) {
+  Prep s{};
+  s.bg = !bins || pl->do_bg;
+  s.seg = bins && pl->do_seg;
+  s.lds = s.bg && pl->lds_hist;
+  s.bins = bins && !pl->cnt;
+  s.filt = pl->K.ann_want >= 0 || pl->K.has_start || pl->K.has_end;
+  s.fst = bins && prep_sums_fst(pl);   // Fst sums with a plan's pass; not in sfs2d_bg_hist
   // the joint-histogram variant (plan_create sets K.jnt, with hr = 1)
-  if constexpr (B && L && !N && !F && !FS) {
-    if (pl->K.jnt && pl->hr == 1) return go(k_prep<B, S, L, N, F, FS, true>);
-  }
-  return go(k_prep<B, S, L, N, F, FS>);
+  s.jnt = s.lds && !s.bins && !s.filt && !s.fst && pl->K.jnt && pl->hr == 1;
+  return s;
 }
 
-template <bool B, bool S, bool L, bool N, bool F>
-hipError_t launch_prep2(sfs2d_plan* pl) {
-  // Fst sums with a plan's pass (the bins pass, or a counts plan's bins-less one); not in sfs2d_bg_hist
-  if (pl->fst && !pl->fst_win && !pl->fst_scan && (N || pl->cnt)) return launch_prep3<B, S, L, N, F, true>(pl);
-  return launch_prep3<B, S, L, N, F, false>(pl);
-}
-
-template <bool B, bool S, bool L, bool N>
-hipError_t launch_prep1(sfs2d_plan* pl) {
-  const bool f = pl->K.ann_want >= 0 || pl->K.has_start || pl->K.has_end;
-  return f ? launch_prep2<B, S, L, N, true>(pl) : launch_prep2<B, S, L, N, false>(pl);
-}
-
-// k_prep for a plan run: a counts plan's pass stores no bins (and is skipped when it has nothing to do:
-// supplied background, SNP-count windows, no Fst sums)
-hipError_t launch_prep_cnt(sfs2d_plan* pl) {
-  const bool L = pl->lds_hist;
-  const bool fs = pl->fst && !pl->fst_win && !pl->fst_scan;
-  if (pl->do_bg && pl->do_seg)
-    return L ? launch_prep1<true, true, true, false>(pl) : launch_prep1<true, true, false, false>(pl);
-  if (pl->do_bg) return L ? launch_prep1<true, false, true, false>(pl) : launch_prep1<true, false, false, false>(pl);
-  if (pl->do_seg) return launch_prep1<false, true, false, false>(pl);
-  if (fs) return launch_prep1<false, false, false, false>(pl);
-  return hipSuccess;
+int launch_prep(sfs2d_plan* pl, bool bins) {
+  if (bins ? !prep_runs(pl) : pl->tiles.empty()) return 0;
+  const sfs2d_data* d = pl->data;
+  const Prep s = prep_sel(pl, bins);
+  int rc = 0;
+  const Prep::Fn k = variant(pl->ctx, s, "k_prep", &rc);
+  if (!k) return rc;
+  hipExtLaunchKernelGGL(k, dim3((unsigned)pl->tiles.size()), dim3(BLOCK1),
+                     s.lds ? pl->bg_lds : 0, CTX_STREAM(pl->ctx), pl->kev[0], pl->kev[1], 0, pl->K, d->counts, d->pos, d->ann, pl->d_tiles,
+                     pl->d_repl + (size_t)repl_par(pl) * REPL * pl->K.nchrom * pl->K.nh, pl->d_slots, pl->d_bins,
+                     pl->d_bcount + (size_t)plan_par(pl) * pl->K.nchrom, pl->d_err, s.lds ? pl->hr : 1,
+                     reinterpret_cast<const double2*>(pl->ctx->d_df + 2 * LNT), pl->d_fsum);
+  HIPCHK(pl->ctx, hipGetLastError());
+  return 0;
 }
 
 // whether a run takes its slot table from the generator's window offsets or a binary search on the
 // positions instead of k_prep (seg_synth / seg_search; k_prep's Fst sums or an attached plan's use of its
 // pass keep k_prep)
 bool slots_only(const sfs2d_plan* pl) {
-  return (pl->seg_synth || pl->seg_search) && pl->attached.empty() && !(pl->fst && !pl->fst_win && !pl->fst_scan);
+  return (pl->seg_synth || pl->seg_search) && pl->attached.empty() && !prep_sums_fst(pl);
 }
 
 hipError_t launch_slots_only(sfs2d_plan* pl) {
@@ -497,11 +582,6 @@ hipError_t stage_slots(sfs2d_plan* pl) {
   return e;
 }
 
-// whether a plan run launches k_prep at all
-bool prep_runs(const sfs2d_plan* pl) {
-  return !pl->tiles.empty() && (!pl->cnt || pl->do_bg || pl->do_seg || (pl->fst && !pl->fst_win && !pl->fst_scan));
-}
-
 // a sliding plan's slot table (after k_prep, which does not segment for it).  ev: with the k_prep timing
 // events, when the run launches no k_prep (this is then its segmentation stage, as launch_slots_only)
 hipError_t launch_slots_slide(sfs2d_plan* pl, bool ev) {
@@ -528,18 +608,6 @@ hipError_t launch_fst_win(sfs2d_plan* a) {
   return hipGetLastError();
 }
 
-hipError_t launch_prep(sfs2d_plan* pl, bool bins) {
-  if (pl->tiles.empty()) return hipSuccess;
-  const bool L = pl->lds_hist;
-  if (!bins) return L ? launch_prep1<true, false, true, false>(pl) : launch_prep1<true, false, false, false>(pl);
-  if (pl->cnt) return launch_prep_cnt(pl);
-  if (pl->do_bg && pl->do_seg)
-    return L ? launch_prep1<true, true, true, true>(pl) : launch_prep1<true, true, false, true>(pl);
-  if (pl->do_bg) return L ? launch_prep1<true, false, true, true>(pl) : launch_prep1<true, false, false, true>(pl);
-  if (pl->do_seg) return launch_prep1<false, true, false, true>(pl);
-  return launch_prep1<false, false, false, true>(pl);
-}
-
 // per-run per-chromosome backgrounds
 hipError_t launch_bg_slices(sfs2d_plan* pl) {
   hipExtLaunchKernelGGL(k_bg_slice, dim3((unsigned)pl->slices.size() + 1 + (unsigned)pl->nfst, (unsigned)pl->nbg), dim3(KBLOCK), 0,
@@ -559,30 +627,25 @@ hipError_t launch_finalize(sfs2d_plan* pl, int integer_values) {
   return hipGetLastError();
 }
 
-template <bool P16, bool CNT>
-hipError_t launch_extra(sfs2d_plan* pl, sfs2d_window* out) {
+int launch_scan_any(sfs2d_plan* pl, sfs2d_window* out) {
+  int rc = pl->chunks.empty() ? 0 : launch_scan(pl, out);
+  if (rc || pl->extra_rec < 0) return rc;
   const sfs2d_data* d = pl->data;
-  hipLaunchKernelGGL((k_scan_extra<P16, CNT>), dim3(1), dim3(WAVE), pl->extra_lds, CTX_STREAM(pl->ctx), pl->K, scan_src(pl),
+  const ScanExtra::Fn k = variant(pl->ctx, scan_extra_sel(pl), "k_scan_extra", &rc);
+  if (!k) return rc;
+  hipLaunchKernelGGL(k, dim3(1), dim3(WAVE), pl->extra_lds, CTX_STREAM(pl->ctx), pl->K, scan_src(pl),
                      d->pos, pl->last_chrom, d->d_chrom_off, pl->d_tab, pl->d_head,
                      pl->prm.bg_mode == SFS2D_BG_PER_CHROM ? 1 : 0, pl->ctx->d_lnx, out, (long long)pl->extra_rec);
-  return hipGetLastError();
-}
-
-hipError_t launch_scan_any(sfs2d_plan* pl, sfs2d_window* out) {
-  hipError_t e = hipSuccess;
-  if (!pl->chunks.empty()) e = pl->p16 ? launch_scan<true>(pl, out) : launch_scan<false>(pl, out);
-  if (e == hipSuccess && pl->extra_rec >= 0)
-    e = pl->p16 ? (pl->cnt ? launch_extra<true, true>(pl, out) : launch_extra<true, false>(pl, out))
-                : (pl->cnt ? launch_extra<false, true>(pl, out) : launch_extra<false, false>(pl, out));
-  return e;
+  HIPCHK(pl->ctx, hipGetLastError());
+  return 0;
 }
 
 // one attached plan inside its base's run: its window slots (fixed bp: binary search on the
 // positions), its Fst sums (from the base's), then its scan against the base's k_prep output
-hipError_t launch_attached(sfs2d_plan* a) {
+int launch_attached(sfs2d_plan* a) {
   const sfs2d_data* d = a->data;
   const uint32_t ns = (uint32_t)a->nslots;
-  if (!ns) { a->runs++; return hipSuccess; }
+  if (!ns) { a->runs++; return 0; }
   const dim3 g((ns + 255) / 256);
   if (a->step)
     hipLaunchKernelGGL(k_slots_slide, g, dim3(256), 0, CTX_STREAM(a->ctx), d->pos, d->d_chrom_off, a->d_slot_base,
@@ -595,10 +658,10 @@ hipError_t launch_attached(sfs2d_plan* a) {
                        a->d_slot_base, d->nchrom, a->fst_m, ns,
                        std::max(0, a->base->K.fst_e - a->K.fst_e), a->d_fsum);
   if (a->fst_win) launch_fst_win(a);   // before the scan clears the slots
-  const hipError_t e = launch_scan_any(a, a->d_out);
+  const int rc = launch_scan_any(a, a->d_out);
   a->last_out = a->d_out;
   a->runs++;
-  return e;
+  return rc;
 }
 
 }  // namespace
@@ -961,6 +1024,22 @@ static int make_kparams(sfs2d_ctx* ctx, const sfs2d_params* prm, int nchrom, KPa
   return 0;
 }
 
+// plan_create's environment knobs, read once per plan (null: not set); each is parsed where it applies
+struct Knobs {
+  const char* seg = std::getenv("SFS2D_SEG");                // prep / search / index: where fixed-bp slots come from
+  const char* lnl = std::getenv("SFS2D_LNL");                // 0: k_scan_gw without its LDS ln table
+  const char* gw = std::getenv("SFS2D_GW");                  // 0 / 1: large grids by k_scan_g / k_scan_gw
+  const char* fused = std::getenv("SFS2D_FUSED");            // 0 / 1: small-grid tables sliced / fused
+  const char* fst_scan = std::getenv("SFS2D_FST_SCAN");      // 0: Fst from k_prep's sums, not summed in the scan
+  const char* lean = std::getenv("SFS2D_LEAN");              // 0: the gated variants where the lean ones apply
+  const char* slots_once = std::getenv("SFS2D_SLOTS_ONCE");  // 0: index plans write their slot table every run
+  const char* wgs = std::getenv("SFS2D_WGS");                // tuning: scan workgroups in all
+  const char* gwwin = std::getenv("SFS2D_GWWIN");            // tuning: k_scan_gw windows per workgroup of a small chromosome
+  const char* pools = std::getenv("SFS2D_POOLS");            // tuning: most window pools per chromosome
+  const char* tile = std::getenv("SFS2D_TILE");              // tuning: SNPs per k_prep tile
+  const char* jnt = std::getenv("SFS2D_JNT");                // 0 / 1: k_prep's joint histogram never / whatever the tile size
+};
+
 static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, int force_sliced, int64_t step,
                        sfs2d_plan** out);
 
@@ -1000,6 +1079,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   KParams K;
   int rc = make_kparams(ctx, prm, data->nchrom, &K);
   if (rc) return rc;
+  const Knobs env;
   const bool slide = step > 0;
   const int64_t adv = slide ? step : prm->window;   // bp from one window's start to the next's
   sfs2d_plan* pl = new sfs2d_plan();
@@ -1050,8 +1130,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // SFS2D_SEG=prep forces k_prep's segmentation, SFS2D_SEG=search the search (never the generator's
   // offsets: what a real replicate VCF gets); both are selected by tests/test_synth_device.py.  SFS2D_SEG=index
   // names what plans with per-chromosome backgrounds take unless it is prep (seg_index below, tests/test_slot_index.py)
-  const char* seg_ev = std::getenv("SFS2D_SEG");
-  const bool seg_prep = seg_ev && std::strcmp(seg_ev, "prep") == 0, seg_srch = seg_ev && std::strcmp(seg_ev, "search") == 0;
+  const bool seg_prep = env.seg && std::strcmp(env.seg, "prep") == 0, seg_srch = env.seg && std::strcmp(env.seg, "search") == 0;
   if (bp && !slide && data->d_win_off && (uint32_t)prm->window == data->win_bp && pl->cnt && !pl->do_bg &&
       pl->nslots == (int64_t)nc * (int64_t)data->win_per_chrom) {
     bool all = true;
@@ -1141,10 +1220,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
       pl->scan_lds = sizeof(double) * (size_t)(((K.nt + 1) & ~1) + LNT + LNF + rt) + hist_words * 4;
       // with the static LDS of the variant that uses most (the batched finish's per-wave arrays, Fst);
       // grids whose workgroup does not fit the 160 KB (e.g. 81 x 81) take the large-grid kernels
-      hipFuncAttributes fa{};
-      const size_t stat = hipFuncGetAttributes(&fa, (const void*)k_scan_w<true, true, true, true>) == hipSuccess
-                              ? fa.sharedSizeBytes : 4096;
-      if (pl->scan_lds + stat > 160 * 1024) pl->G = 256;
+      if (pl->scan_lds + static_lds(SCAN_W_FIT, 4096) > 160 * 1024) pl->G = 256;
     }
     if (pl->G != WAVE) {
       pl->scan_lds = (size_t)(core + TRASH + 2) * 4 + 32 * 8 + 32 * 8;
@@ -1163,50 +1239,24 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
       size_t gw_lds = (size_t)(h2w + R1GW * (K.n1p + 1) + R1GW * (K.n2p + 1) + TRASH) * 4;
       int occ = 0;
       if (gw_lds <= 160 * 1024) {
-        const hipFuncAttribute A = hipFuncAttributeMaxDynamicSharedMemorySize;
-        if (gw_lds > 64 * 1024)
-          for (const void* f : {(const void*)k_scan_gw<true, false, false>, (const void*)k_scan_gw<false, false, false>,
-                                (const void*)k_scan_gw<true, true, false>, (const void*)k_scan_gw<false, true, false>,
-                                (const void*)k_scan_gw<true, false, true>, (const void*)k_scan_gw<false, false, true>,
-                                (const void*)k_scan_gw<true, true, true>, (const void*)k_scan_gw<false, true, true>,
-                                (const void*)k_scan_gw<true, false, true, true>, (const void*)k_scan_gw<false, false, true, true>,
-                                (const void*)k_scan_gw<true, true, true, true>, (const void*)k_scan_gw<false, true, true, true>})
-            hipFuncSetAttribute(f, A, (int)gw_lds);
-        const hipError_t oe =
-            K.ntri ? (pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<true, true, true, true>, WAVE, gw_lds)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<false, true, true, true>, WAVE, gw_lds))
-                   : (pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<true, true, true>, WAVE, gw_lds)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<false, true, true>, WAVE, gw_lds));
-        if (oe != hipSuccess) occ = 0;
+        // workgroups per CU of the plan's stand-in with lds bytes of dynamic LDS (0: more than the 160 KB, or no answer)
+        const ScanGW gs = occ_standin(scan_gw_sel(pl));
+        auto gw_occ = [&](size_t lds) {
+          if (lds > 160 * 1024) return 0;
+          if (lds > 64 * 1024) set_max_lds<ScanGW>(lds);
+          return occupancy(gs, WAVE, lds);
+        };
+        occ = gw_occ(gw_lds);
         // the LDS ln table (KParams::lnl) when it costs no workgroup per CU (config 4's 101 x 101 triangle:
         // 16 one-wave workgroups either way; config 5's 201 x 151 grid would lose one)
-        {
-          const size_t lds2 = gw_lds + 8 + (size_t)LNL * 8;
-          int occ2 = 0;
-          const bool big = lds2 > 64 * 1024 && lds2 <= 160 * 1024;
-          if (big)
-            for (const void* f : {(const void*)k_scan_gw<true, false, false>, (const void*)k_scan_gw<false, false, false>,
-                                  (const void*)k_scan_gw<true, true, false>, (const void*)k_scan_gw<false, true, false>,
-                                  (const void*)k_scan_gw<true, false, true>, (const void*)k_scan_gw<false, false, true>,
-                                  (const void*)k_scan_gw<true, true, true>, (const void*)k_scan_gw<false, true, true>,
-                                  (const void*)k_scan_gw<true, false, true, true>, (const void*)k_scan_gw<false, false, true, true>,
-                                  (const void*)k_scan_gw<true, true, true, true>, (const void*)k_scan_gw<false, true, true, true>})
-              hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-          const hipError_t oe2 =
-              lds2 > 160 * 1024 ? hipErrorInvalidValue
-              : K.ntri ? (pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, k_scan_gw<true, true, true, true>, WAVE, lds2)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, k_scan_gw<false, true, true, true>, WAVE, lds2))
-                       : (pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, k_scan_gw<true, true, true>, WAVE, lds2)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, k_scan_gw<false, true, true>, WAVE, lds2));
-          const char* lev = std::getenv("SFS2D_LNL");
-          if (oe2 == hipSuccess && occ2 == occ && occ >= 2 && !(lev && lev[0] == '0')) {
-            gw_lds = lds2;
-            K.lnl = pl->K.lnl = 1;
-          }
-          (void)hipGetLastError();
+        const size_t lds2 = gw_lds + 8 + (size_t)LNL * 8;
+        if (gw_occ(lds2) == occ && occ >= 2 && !(env.lnl && env.lnl[0] == '0')) {
+          gw_lds = lds2;
+          K.lnl = pl->K.lnl = 1;
         }
+        (void)hipGetLastError();
         pl->gw = occ >= 2;   // measured on 201 x 151 with u16 bins (2 per CU): 22 vs 32 us for k_scan_g
-        if (const char* ev = std::getenv("SFS2D_GW")) pl->gw = occ >= 1 && ev[0] == '1';
+        if (env.gw) pl->gw = occ >= 1 && env.gw[0] == '1';
       }
       if (pl->gw) pl->scan_lds = gw_lds;
     }
@@ -1227,7 +1277,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   const bool small = pl->do_bg && pl->G == WAVE;
   const double wpw = (double)pl->nslots / (2.0 * ctx->ncu * (SBLOCK / WAVE));   // windows per resident wave
   pl->sliced = small && wpw < 4.0;
-  if (const char* ev = std::getenv("SFS2D_FUSED")) pl->sliced = small && ev[0] == '0';
+  if (env.fused) pl->sliced = small && env.fused[0] == '0';
   if (force_sliced >= 0) pl->sliced = small && force_sliced == 1;
   pl->fused = small && !pl->sliced;
   // Fst of sliced fixed-bp plans: by extra k_bg_slice workgroups (the GPU is mostly idle during
@@ -1243,13 +1293,9 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // Fst workgroups instead (attached Fst then needs fixed-bp windows the base's divide)
   pl->fst_scan = false;
   if (pl->fst && pl->cnt && pl->G == WAVE && !pl->gw) {
-    const char* ev = std::getenv("SFS2D_FST_SCAN");
-    pl->fst_scan = !(ev && ev[0] == '0');
-    if (pl->fst_scan) {   // its variant's static LDS must fit beside the dynamic
-      hipFuncAttributes fa{};
-      const void* f = pl->p16 ? (const void*)k_scan_w<true, true, 2, true> : (const void*)k_scan_w<false, true, 2, true>;
-      if (hipFuncGetAttributes(&fa, f) != hipSuccess || pl->scan_lds + fa.sharedSizeBytes > 160 * 1024) pl->fst_scan = false;
-    }
+    pl->fst_scan = !(env.fst_scan && env.fst_scan[0] == '0');
+    // its variant's static LDS must fit beside the dynamic (a failed query: no Fst in the scan)
+    if (pl->fst_scan && pl->scan_lds + static_lds(scan_w_fst_fit(pl->p16), 160 * 1024) > 160 * 1024) pl->fst_scan = false;
   }
   // folded, and every called count within 2 pop_size (the condition of k_scan_gw's triangle below): a
   // folded key has x1 <= n1, x2 <= n2 and x1 + x2 <= (n1 + n2) / 2 -- inside the grid and never the excluded
@@ -1259,7 +1305,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // gated plans whose windows come from fixed-bp slot records and whose folded 1D spectra fit one half-wave
   // each: the LEAN variants (SFS2D_LEAN=0: the gated variants, for comparison -- the results are the same)
   pl->lean = pl->gate && bp && K.n1p <= 31 && K.n2p <= 31;
-  if (const char* ev = std::getenv("SFS2D_LEAN")) pl->lean = pl->lean && ev[0] != '0';
+  if (env.lean) pl->lean = pl->lean && env.lean[0] != '0';
   const PwTree pw = pw_plan(K.nb2 - 3);
   pl->fst_mask = data->low_nc;
   pl->fst_win = pl->sliced && bp && pl->fst && !pl->fst_scan;
@@ -1275,7 +1321,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // be written after the plan is created, in stream order ahead of a run (tests/test_stream_contract.py), or
   // between runs, so no index built from them once holds; they keep k_prep's segmentation.
   pl->seg_index = bp && !slide && pl->cnt && pl->do_bg && !seg_prep && force_sliced < 0 && data->owned &&
-                  !(pl->fst && !pl->fst_win && !pl->fst_scan);
+                  !prep_sums_fst(pl);
   if (pl->seg_index) {
     if ((rc = data_pos_index(ctx, data))) { delete pl; return rc; }
     pl->do_seg = false;
@@ -1283,42 +1329,13 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // ... and with Fst summed in the scan no kernel but k_slots_index stores to the table (the scan's slot clear
   // is the Fst-free variants'): it is written once per plan.  SFS2D_SLOTS_ONCE=0: every run, for comparison
   pl->slots_once = pl->seg_index && pl->fst_scan;
-  if (const char* ev = std::getenv("SFS2D_SLOTS_ONCE")) pl->slots_once = pl->slots_once && ev[0] != '0';
+  if (env.slots_once) pl->slots_once = pl->slots_once && env.slots_once[0] != '0';
   pl->nfst = pl->fst_win && !slide ? (int)std::min<int64_t>(1024, std::max<int64_t>(1, (pl->nslots + 7) / 8)) : 0;   // ~1 window per wave
-  if (pl->scan_lds > 64 * 1024) {
-    const int lds = (int)pl->scan_lds;
-    const hipFuncAttribute A = hipFuncAttributeMaxDynamicSharedMemorySize;
-    for (const void* f : {(const void*)k_scan_w<true, true, false, false>, (const void*)k_scan_w<false, true, false, false>,
-                          (const void*)k_scan_w<true, false, false, false>, (const void*)k_scan_w<false, false, false, false>,
-                          (const void*)k_scan_w<true, true, true, false>, (const void*)k_scan_w<false, true, true, false>,
-                          (const void*)k_scan_w<true, false, true, false>, (const void*)k_scan_w<false, false, true, false>,
-                          (const void*)k_scan_w<true, true, false, true>, (const void*)k_scan_w<false, true, false, true>,
-                          (const void*)k_scan_w<true, false, false, true>, (const void*)k_scan_w<false, false, false, true>,
-                          (const void*)k_scan_w<true, true, true, true>, (const void*)k_scan_w<false, true, true, true>,
-                          (const void*)k_scan_w<true, false, true, true>, (const void*)k_scan_w<false, false, true, true>,
-                          (const void*)k_scan_w<true, true, 2, true>, (const void*)k_scan_w<false, true, 2, true>,
-                          (const void*)k_scan_w<true, false, 2, true>, (const void*)k_scan_w<false, false, 2, true>,
-                          (const void*)k_scan_w<true, true, 3, true>, (const void*)k_scan_w<false, true, 3, true>,
-                          (const void*)k_scan_w<true, false, 3, true>, (const void*)k_scan_w<false, false, 3, true>,
-                          (const void*)k_scan_w<true, true, 2, true, true>, (const void*)k_scan_w<false, true, 2, true, true>,
-                          (const void*)k_scan_w<true, false, 2, true, true>, (const void*)k_scan_w<false, false, 2, true, true>,
-                          (const void*)k_scan_w<true, true, 3, true, true>, (const void*)k_scan_w<false, true, 3, true, true>,
-                          (const void*)k_scan_w<true, false, 3, true, true>, (const void*)k_scan_w<false, false, 3, true, true>,
-                          (const void*)k_scan_w<true, true, 2, true, true, true>, (const void*)k_scan_w<false, true, 2, true, true, true>,
-                          (const void*)k_scan_w<true, false, 2, true, true, true>, (const void*)k_scan_w<false, false, 2, true, true, true>,
-                          (const void*)k_scan_w<true, true, 3, true, true, true>, (const void*)k_scan_w<false, true, 3, true, true, true>,
-                          (const void*)k_scan_w<true, false, 3, true, true, true>, (const void*)k_scan_w<false, false, 3, true, true, true>,
-                          (const void*)k_scan_g<true, false, false>, (const void*)k_scan_g<false, false, false>,
-                          (const void*)k_scan_g<true, true, false>, (const void*)k_scan_g<false, true, false>,
-                          (const void*)k_scan_g<true, false, true>, (const void*)k_scan_g<false, false, true>,
-                          (const void*)k_scan_g<true, true, true>, (const void*)k_scan_g<false, true, true>})
-      hipFuncSetAttribute(f, A, lds);
+  if (pl->scan_lds > 64 * 1024) {   // (k_scan_gw's: with its occupancy, above)
+    set_max_lds<ScanW>(pl->scan_lds);
+    set_max_lds<ScanG>(pl->scan_lds);
   }
-  if (pl->extra_lds > 64 * 1024) {
-    for (const void* f : {(const void*)k_scan_extra<true, false>, (const void*)k_scan_extra<false, false>,
-                          (const void*)k_scan_extra<true, true>, (const void*)k_scan_extra<false, true>})
-      hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->extra_lds);
-  }
+  if (pl->extra_lds > 64 * 1024) set_max_lds<ScanExtra>(pl->extra_lds);
 
   // scan work items.  k_scan_w: about one workgroup per resident slot (one dispatch wave, no
   // tail), shared among the chromosomes by window count; each wavefront takes one static window,
@@ -1326,48 +1343,18 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // each other, so static chunks left the slowest workgroups 2x behind the median).
   // k_scan_g: two windows per workgroup.
   if (pl->G == WAVE || pl->gw) {
-    int occ = 0;
-    // (the grid is one dispatch wave of resident workgroups: occupancy of the variant that runs)
-    hipError_t oe;
-    if (pl->gw && K.ntri)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<true, true, true, true>, WAVE, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<false, true, true, true>, WAVE, pl->scan_lds);
-    else if (pl->gw)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<true, true, true>, WAVE, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_gw<false, true, true>, WAVE, pl->scan_lds);
-    else if (pl->lean && pl->fused)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, true, 2, true, true, true>, SBLOCK, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, true, 2, true, true, true>, SBLOCK, pl->scan_lds);
-    else if (pl->lean)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, false, 2, true, true, true>, SBLOCK, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, false, 2, true, true, true>, SBLOCK, pl->scan_lds);
-    else if (pl->gate && pl->fused)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, true, 2, true, true>, SBLOCK, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, true, 2, true, true>, SBLOCK, pl->scan_lds);
-    else if (pl->gate)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, false, 2, true, true>, SBLOCK, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, false, 2, true, true>, SBLOCK, pl->scan_lds);
-    else if (pl->fst_scan && pl->fused)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, true, 2, true>, SBLOCK, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, true, 2, true>, SBLOCK, pl->scan_lds);
-    else if (pl->fst_scan)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, false, 2, true>, SBLOCK, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, false, 2, true>, SBLOCK, pl->scan_lds);
-    else if (pl->fused)
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, true, true, true>, SBLOCK, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, true, true, true>, SBLOCK, pl->scan_lds);
-    else
-      oe = pl->p16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<true, false, true, true>, SBLOCK, pl->scan_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_w<false, false, true, true>, SBLOCK, pl->scan_lds);
-    if (oe != hipSuccess || occ < 1) occ = 1;
+    // (the grid is one dispatch wave of resident workgroups: occupancy of the variant's stand-in, occ_standin)
+    int occ = pl->gw ? occupancy(occ_standin(scan_gw_sel(pl)), WAVE, pl->scan_lds)
+                     : occupancy(occ_standin(scan_w_sel(pl)), SBLOCK, pl->scan_lds);
+    if (occ < 1) occ = 1;
     if (prm->scan_wgs_per_cu > 0 && (int)prm->scan_wgs_per_cu < occ) occ = (int)prm->scan_wgs_per_cu;
     int64_t cap = (int64_t)occ * ctx->ncu;
     if (pl->gw) pl->nscr = (int)cap;   // one exact-path histogram per resident wavefront
-    if (const char* ev = std::getenv("SFS2D_WGS")) cap = std::max<int64_t>(1, std::atoll(ev));   // tuning
+    if (env.wgs) cap = std::max<int64_t>(1, std::atoll(env.wgs));
     const double S = (double)std::max<unsigned long long>(1, slot_base[nc] - slot_base[0]);
     const uint32_t NW = pl->gw ? 1u : (uint32_t)(SBLOCK / WAVE);   // wavefronts per workgroup
     int64_t gw_win = 64;   // k_scan_gw: windows per workgroup of a small chromosome
-    if (const char* ev = std::getenv("SFS2D_GWWIN")) gw_win = std::max<int64_t>(1, std::atoll(ev));   // tuning
+    if (env.gwwin) gw_win = std::max<int64_t>(1, std::atoll(env.gwwin));
     std::vector<double> order;
     for (int c = 0; c < nc; ++c) {
       const uint32_t ns = (uint32_t)(slot_base[c + 1] - slot_base[c]);
@@ -1380,7 +1367,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
       if (pl->gw) want = std::max<int64_t>(want, (ns + gw_win - 1) / gw_win);
       const uint32_t nwg = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(wmax, want));
       uint32_t npool = std::min<uint32_t>(nwg, CTR_POOLS);
-      if (const char* ev = std::getenv("SFS2D_POOLS")) npool = std::max(1u, std::min<uint32_t>(npool, (uint32_t)std::atoi(ev)));   // tuning
+      if (env.pools) npool = std::max(1u, std::min<uint32_t>(npool, (uint32_t)std::atoi(env.pools)));
       for (uint32_t k = 0; k < nwg; ++k) {
         Chunk ch{};
         ch.chrom = (uint32_t)c; ch.slot_lo = (uint32_t)slot_base[c]; ch.slot_hi = (uint32_t)slot_base[c + 1];
@@ -1421,10 +1408,9 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     // ~1000+ tiles for big inputs (several workgroups per CU), >= 4096 SNPs each (flush amortised)
     // (with k_prep's Fst sums, <= 32k SNPs per tile keep a tile's windows in its LDS sums down to
     // ~128-SNP windows; every tile flushes its LDS histogram, so no smaller tiles than that otherwise)
-    const bool kfst_t = (prm->flags & SFS2D_F_FST) && !pl->fst_win && !pl->fst_scan;
-    const int64_t Tmax = kfst_t ? 32768 : 65536;
+    const int64_t Tmax = prep_sums_fst(pl) ? 32768 : 65536;
     int64_t T = std::max<int64_t>(4096, std::min<int64_t>(Tmax, (n / 768 + 4095) / 4096 * 4096));
-    if (const char* ev = std::getenv("SFS2D_TILE")) T = std::max<int64_t>(2048, std::atoll(ev) & ~int64_t(3));   // tuning
+    if (env.tile) T = std::max<int64_t>(2048, std::atoll(env.tile) & ~int64_t(3));
     tileT = T;
     // tile edges on absolute multiples of 4 SNPs (T is): only a chromosome's first and last step
     // take k_prep's masked edge path, every interior step of every tile the fast one
@@ -1450,20 +1436,16 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     // the LDS histogram must fit beside the static LDS of the k_prep variant that will run: the Fst
     // variant (Fst not taken from k_bg_slice) holds ~20 KB of window sums and reciprocals, so e.g.
     // pop_size 95 / 95 (148 KB of histogram) takes the global-atomic histogram with Fst
-    const bool kfst = (prm->flags & SFS2D_F_FST) && !pl->fst_win && !pl->fst_scan;
-    hipFuncAttributes fa{};
-    const hipError_t ae = kfst ? hipFuncGetAttributes(&fa, (const void*)k_prep<true, true, true, true, false, true>)
-                               : hipFuncGetAttributes(&fa, (const void*)k_prep<true, true, true, true, false, false>);
-    const size_t stat = ae == hipSuccess ? fa.sharedSizeBytes : (kfst ? 24 * 1024 : 1024);
+    const bool kfst = prep_sums_fst(pl);
+    const size_t stat = static_lds(prep_lds_fit(kfst), kfst ? 24 * 1024 : 1024);
     pl->lds_hist = pl->bg_lds + stat <= 160 * 1024;
     // k_prep's joint (alt1, alt2) histogram (prep_tile, JNT): counts plans whose k_prep only histograms
     // and segments, with tiles of >= 16k SNPs (its margins pass at the tile's end cost config 2's 4k-SNP
     // tiles more than the atomics saved: 2.25e8 vs 2.32-2.46e8 windows/s, profiles/r06i_prep_joint_hist.txt),
     // while the LDS stays <= 64 KB (nb2 words more).  SFS2D_JNT=0: three atomics per SNP; =1: the joint
     // histogram whatever the tile size (tests)
-    const char* jev = std::getenv("SFS2D_JNT");
     const size_t jl = pl->bg_lds + (size_t)K.nb2 * 4;
-    const bool jwant = jev ? jev[0] == '1' : tileT >= 16384;
+    const bool jwant = env.jnt ? env.jnt[0] == '1' : tileT >= 16384;
     // (one histogram copy per word: the joint path indexes the LDS histogram unreplicated; a counts plan has
     // no filter, so its histogram pass always launches the JNT instantiation and uses these nb2 words)
     if (pl->lds_hist && pl->hr == 1 && pl->cnt && !kfst && jl + stat <= 64 * 1024 && jwant) {
@@ -1471,28 +1453,10 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
       pl->bg_lds = jl;
     }
   }
-  if (pl->lds_hist && pl->bg_lds > 64 * 1024) {
-    const hipFuncAttribute A = hipFuncAttributeMaxDynamicSharedMemorySize;
-    const int lds = (int)pl->bg_lds;
-    hipError_t e = hipSuccess;
-    auto set = [&](const void* f) { if (e == hipSuccess) e = hipFuncSetAttribute(f, A, lds); };
-    set((const void*)k_prep<true, true, true, true, false, false>);
-    set((const void*)k_prep<true, false, true, true, false, false>);
-    set((const void*)k_prep<true, true, true, true, true, false>);
-    set((const void*)k_prep<true, false, true, true, true, false>);
-    set((const void*)k_prep<true, true, true, true, false, true>);
-    set((const void*)k_prep<true, false, true, true, false, true>);
-    set((const void*)k_prep<true, true, true, true, true, true>);
-    set((const void*)k_prep<true, false, true, true, true, true>);
-    set((const void*)k_prep<true, false, true, false, false, false>);   // (the histogram-only pass)
-    set((const void*)k_prep<true, false, true, false, true, false>);
-    set((const void*)k_prep<true, true, true, false, false, false>);    // (counts plans: no bins)
-    set((const void*)k_prep<true, true, true, false, false, true>);
-    set((const void*)k_prep<true, false, true, false, false, true>);
-    if (e != hipSuccess) {   // the large dynamic LDS was refused: the global-atomic histogram instead
-      (void)hipGetLastError();
-      pl->lds_hist = false;
-    }
+  // the large dynamic LDS refused: the global-atomic histogram instead
+  if (pl->lds_hist && pl->bg_lds > 64 * 1024 && set_max_lds<Prep>(pl->bg_lds) != hipSuccess) {
+    (void)hipGetLastError();
+    pl->lds_hist = false;
   }
   hipFuncSetAttribute((const void*)k_bg_finalize, hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)(sizeof(double) * FIN_LDS_BINS));
@@ -1632,7 +1596,7 @@ int sfs2d_plan_run_phase(sfs2d_plan* pl, int phase, sfs2d_window* out_dev) {
       if (pl->nslots == 0 && (rc = mark(0))) return rc;
     } else {
       if (pl->seg_index) HIPCHK(ctx, stage_slots(pl));
-      HIPCHK(ctx, launch_prep(pl, true));
+      if ((rc = launch_prep(pl, true))) return rc;
       const bool slots = pl->step && pl->nslots;   // a sliding plan's table, after k_prep
       if (slots) HIPCHK(ctx, launch_slots_slide(pl, !prep_runs(pl)));
       if (!prep_runs(pl) && !slots && (rc = mark(0))) return rc;
@@ -1642,10 +1606,11 @@ int sfs2d_plan_run_phase(sfs2d_plan* pl, int phase, sfs2d_window* out_dev) {
     if (pl->do_bg && !pl->fused) HIPCHK(ctx, launch_bg_slices(pl));
     else if ((rc = mark(2))) return rc;
     if (pl->step && pl->fst_win) HIPCHK(ctx, launch_fst_win(pl));   // (the scan may clear the slots)
-    for (sfs2d_plan* a : pl->attached) HIPCHK(ctx, launch_attached(a));   // before the base clears its state
+    for (sfs2d_plan* a : pl->attached)   // before the base clears its state
+      if ((rc = launch_attached(a))) return rc;
     sfs2d_window* out = out_dev ? out_dev : pl->d_out;
     if (pl->chunks.empty() && (rc = mark(4))) return rc;
-    HIPCHK(ctx, launch_scan_any(pl, out));
+    if ((rc = launch_scan_any(pl, out))) return rc;
     pl->last_out = out;
     pl->runs++;
   }
@@ -2229,17 +2194,20 @@ int sfs2d_plan_time(sfs2d_plan* pl, int iters, double* ms_run, double* ms_k1, do
   sfs2d_ctx* ctx = pl->ctx;
   hipStream_t st = CTX_STREAM(ctx);
   double t1 = 0, t2 = 0, t3 = 0, tall = 0;
+  int rc = 0;
   for (int it = 0; it < iters; ++it) {
     HIPCHK(ctx, hipEventRecord(pl->ev[0], st));
     if (pl->seg_index) HIPCHK(ctx, stage_slots(pl));
-    HIPCHK(ctx, slots_only(pl) ? launch_slots_only(pl) : launch_prep(pl, true));
+    if (slots_only(pl)) HIPCHK(ctx, launch_slots_only(pl));
+    else if ((rc = launch_prep(pl, true))) return rc;
     if (pl->step) HIPCHK(ctx, launch_slots_slide(pl, false));
     HIPCHK(ctx, hipEventRecord(pl->ev[1], st));
     if (pl->do_bg && !pl->fused) HIPCHK(ctx, launch_bg_slices(pl));
     if (pl->step && pl->fst_win) HIPCHK(ctx, launch_fst_win(pl));
-    for (sfs2d_plan* a : pl->attached) HIPCHK(ctx, launch_attached(a));
+    for (sfs2d_plan* a : pl->attached)
+      if ((rc = launch_attached(a))) return rc;
     HIPCHK(ctx, hipEventRecord(pl->ev[2], st));
-    HIPCHK(ctx, launch_scan_any(pl, pl->d_out));
+    if ((rc = launch_scan_any(pl, pl->d_out))) return rc;
     pl->runs++;
     HIPCHK(ctx, hipEventRecord(pl->ev[3], st));
     HIPCHK(ctx, hipEventSynchronize(pl->ev[3]));
@@ -2423,16 +2391,15 @@ static int bg_hist_impl(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_para
     if (e == hipSuccess) e = hipMemsetAsync(pl.d_repl, 0, sizeof(uint32_t) * REPL * K.nh, CTX_STREAM(ctx));
     if (e == hipSuccess) e = hipMemsetAsync(pl.d_err, 0, 4, CTX_STREAM(ctx));
     if (e == hipSuccess) e = hipMemsetAsync(pl.d_bcount, 0, 4, CTX_STREAM(ctx));
-    if (e == hipSuccess && pl.lds_hist && pl.bg_lds > 64 * 1024)
-      hipFuncSetAttribute((const void*)k_prep<true, false, true, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.bg_lds),
-      hipFuncSetAttribute((const void*)k_prep<true, false, true, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.bg_lds);
-    if (e == hipSuccess) e = launch_prep(&pl, false);
-    if (e == hipSuccess && d_row) {
+    if (e == hipSuccess && pl.lds_hist && pl.bg_lds > 64 * 1024) set_max_lds<Prep>(pl.bg_lds);
+    if (e == hipSuccess) rc = launch_prep(&pl, false);
+    // (rc: a selection outside the table launched nothing; reported below, after the buffers are freed)
+    if (!rc && e == hipSuccess && d_row) {
       const int W = K.h1b + K.n2 + 2;
       hipLaunchKernelGGL(k_bg_rows_get, dim3((unsigned)((W + 255) / 256), 1u), dim3(256), 0, CTX_STREAM(ctx), pl.K,
                          pl.d_repl, (unsigned long long)K.nh, pl.d_bcount, (long long*)d_row, (long long)W);
       e = hipGetLastError();
-    } else if (e == hipSuccess) {
+    } else if (!rc && e == hipSuccess) {
       e = hipMemcpyAsync(hist.data(), pl.d_repl, sizeof(uint32_t) * REPL * K.nh, hipMemcpyDeviceToHost, CTX_STREAM(ctx));
     }
     uint32_t err = 0;

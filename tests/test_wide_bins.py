@@ -9,13 +9,15 @@ launch recorded) against the tuple written in its table, compares every record a
 ScanConfig on uploaded data, where the positions prove P16 = true, and asserts that the two tables agree in every
 integer field and flag.
 
-The P16 = false instantiations launch_scan_c / launch_extra can dispatch (sfs2d.hip), all asserted below:
+The P16 = false instantiations launch_scan / launch_scan_any can select (sfs2d.hip), all asserted below:
 
   k_scan_w<false, FUSED, FST, CNT, GATE>      (FUSED 1: SFS2D_FUSED=1; 0: SFS2D_FUSED=0 or a supplied background)
     Fst in the scan (counts plans):  <F, 2, 1, 1>  folded, called counts within 2 pop_size        fst_gate, wgs1, bgsup_int
                                      <F, 2, 1, 0>  unfolded / over-called data                    fst_unfold, fst_over
                                      <F, 3, 1, 1>  data with < 2 called alleles, folded           fst_mask_gate
                                      <F, 3, 1, 0>  the same, unfolded                             fst_mask_nogate
+      (25 x 25 and 18 x 14 with fixed-bp windows: the gated plans run the LEAN variants, reported as gate = 1;
+       SFS2D_LEAN=0 keeps the gated ones)            <F, 2 | 3, 1, 1> without LEAN     fst_gate_nolean, fst_mask_gate_nolean
     otherwise:                       <F, 0, 1, 0>  counts, no Fst (sliced: also k_fst_win's Fst)  nofst, fst_prep (sliced), sliding
                                      <1, 1, 1, 0>  fused counts, Fst from k_prep's sums           fst_prep (fused)
                                      <0, 1, 1, 0>  supplied background, Fst from k_prep's sums    bgsup_norm
@@ -46,7 +48,8 @@ _DATA, _BG = {}, {}
 
 @pytest.fixture(autouse=True)
 def _env(monkeypatch):
-    for k in ("SFS2D_GW", "SFS2D_FUSED", "SFS2D_FST_SCAN", "SFS2D_SEG", "SFS2D_TILE", "SFS2D_WGS", "SFS2D_LNL"):
+    for k in ("SFS2D_GW", "SFS2D_FUSED", "SFS2D_FST_SCAN", "SFS2D_SEG", "SFS2D_TILE", "SFS2D_WGS", "SFS2D_LNL",
+              "SFS2D_LEAN"):
         monkeypatch.delenv(k, raising=False)
 
 
@@ -103,6 +106,8 @@ W_CASES = {
     "fst_over": ("over", dict(fst=True), {}, None, (2, 1, 0), (2, 1, 0)),
     "fst_mask_gate": ("lownc", dict(fst=True), {}, None, (3, 1, 1), (3, 1, 1)),
     "fst_mask_nogate": ("lownc", dict(fst=True, fold=False), {}, None, (3, 1, 0), (3, 1, 0)),
+    "fst_gate_nolean": ("plain", dict(fst=True), {"SFS2D_LEAN": "0"}, None, (2, 1, 1), (2, 1, 1)),
+    "fst_mask_gate_nolean": ("lownc", dict(fst=True), {"SFS2D_LEAN": "0"}, None, (3, 1, 1), (3, 1, 1)),
     "fst_prep": ("plain", dict(fst=True), {"SFS2D_FST_SCAN": "0"}, None, (1, 1, 0), (0, 1, 0)),
     "bins_vt": ("plain", dict(fst=True, vt=VT), {}, None, (1, 0, 0), (0, 0, 0)),
     "bins_pos": ("plain", dict(POSF), {}, None, (0, 0, 0), (0, 0, 0)),
