@@ -10,6 +10,8 @@
 // Sliding plans (sfs2d_plan_create_sliding) run k_prep without its segmentation, then k_slots_slide
 // (the overlapping slot table by binary search), the tables, k_fst_win where the scan does not sum
 // Fst itself, and the same scan kernels.
+// After a run, sfs2d_plan_diversity enqueues k_div_win (sfs2d_div.hpp) over the run's records: per-window pi, dxy,
+// Watterson and Tajima sums from the resident counts; it writes its own output alone.
 // All device state a run touches (slot table, background replicas and counters, LDS) is left
 // zeroed by the run itself, so plans replay without memsets.
 #include <hip/hip_runtime.h>
@@ -29,6 +31,7 @@
 
 #include "sfs2d.h"
 #include "sfs2d_kernels.hpp"
+#include "sfs2d_div.hpp"
 
 using namespace sfs2dk;
 
@@ -101,6 +104,7 @@ struct sfs2d_ctx {
   hipStream_t stream = nullptr;
   double* d_lnx = nullptr;
   double* d_df = nullptr;   // D(r), F(x) (LNT each), then (1/k, 1/(k(k-1))) pairs (RCPN)
+  double* d_hw = nullptr;   // 1 / h(n), h(n) = sum_{i=1}^{n-1} 1/i, for n < RCPN (0 below n = 2): k_div_win's Watterson terms
   hipEvent_t stagger = nullptr;   // sfs2d_plan_run_streams: the first run's k_prep, awaited by the second stream
   std::string err;
   std::mutex err_mu;
@@ -242,6 +246,10 @@ struct sfs2d_plan {
   // launch_scan from the selection it launches: {P16, FUSED, FST, CNT, GATE, TRI}, -1 where the kernel has none
   int variant[6] = {-1, -1, -1, -1, -1, -1};
   bool variant_set = false;
+  // diversity (sfs2d_plan_diversity): the plan-owned records and where the last call wrote
+  sfs2d_diversity* d_div = nullptr;
+  const sfs2d_diversity* div_last = nullptr;
+  int64_t div_nrec = -1;                 // records of the last call (-1: none yet)
   uint64_t null_tab_runs = ~0ull;        // fused / sliced plans: the run whose tables of EVERY chromosome are in
                                          // d_tab / d_lp / d_head (their scans keep all but one chromosome's in LDS)
 };
@@ -288,7 +296,7 @@ void plan_free(sfs2d_plan* p) {
   hipFree(p->d_done); hipFree(p->d_bgval); hipFree(p->d_tab); hipFree(p->d_lp); hipFree(p->d_head);
   hipFree(p->d_bg1d); hipFree(p->d_leafsum); hipFree(p->d_leaves); hipFree(p->d_nodes); hipFree(p->d_slices);
   hipFree(p->d_out); hipFree(p->d_err); hipFree(p->d_bins); hipFree(p->d_fst_own); hipFree(p->d_fsum); hipFree(p->d_gscr);
-  hipFree(p->d_ntask); hipFree(p->d_null);
+  hipFree(p->d_ntask); hipFree(p->d_null); hipFree(p->d_div);
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->tev) if (e) hipEventDestroy(e);
 }
@@ -692,13 +700,24 @@ int sfs2d_ctx_create(int device, sfs2d_ctx** out) {
   c->stream = c->own;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->ncu = prop.multiProcessorCount;
-  if (dalloc(c, &c->d_lnx, LNX_N) || dalloc(c, &c->d_df, 2 * LNT + 2 * RCPN)) {
-    hipFree(c->d_lnx); hipStreamDestroy(c->own); delete c; return SFS2D_E_NOMEM;
+  if (dalloc(c, &c->d_lnx, LNX_N) || dalloc(c, &c->d_df, 2 * LNT + 2 * RCPN) || dalloc(c, &c->d_hw, RCPN)) {
+    hipFree(c->d_lnx); hipFree(c->d_df); hipStreamDestroy(c->own); delete c; return SFS2D_E_NOMEM;
+  }
+  {   // 1 / h(n): the harmonic sums in ascending order of i (sfs2d/diversity.py forms the same doubles)
+    std::vector<double> hw(RCPN, 0.0);
+    double h = 0.0;
+    for (int n = 2; n < RCPN; ++n) {
+      h += 1.0 / (double)(n - 1);
+      hw[n] = 1.0 / h;
+    }
+    if (hipMemcpy(c->d_hw, hw.data(), sizeof(double) * RCPN, hipMemcpyHostToDevice) != hipSuccess) {
+      hipFree(c->d_lnx); hipFree(c->d_df); hipFree(c->d_hw); hipStreamDestroy(c->own); delete c; return SFS2D_E_HIP;
+    }
   }
   hipLaunchKernelGGL(k_init_lnx, dim3(LNX_N / 256), dim3(256), 0, c->stream, c->d_lnx, c->d_df, c->d_df + LNT,
                      c->d_df + 2 * LNT);
   if (hipStreamSynchronize(c->stream) != hipSuccess) {
-    hipFree(c->d_lnx); hipFree(c->d_df); hipStreamDestroy(c->own); delete c; return SFS2D_E_HIP;
+    hipFree(c->d_lnx); hipFree(c->d_df); hipFree(c->d_hw); hipStreamDestroy(c->own); delete c; return SFS2D_E_HIP;
   }
   *out = c;
   return 0;
@@ -710,6 +729,7 @@ int sfs2d_ctx_destroy(sfs2d_ctx* ctx) {
   hipStreamSynchronize(CTX_STREAM(ctx));
   hipFree(ctx->d_lnx);
   hipFree(ctx->d_df);
+  hipFree(ctx->d_hw);
   if (ctx->stagger) hipEventDestroy(ctx->stagger);
   hipStreamDestroy(ctx->own);
   delete ctx;
@@ -2184,6 +2204,54 @@ int sfs2d_plan_null_read(sfs2d_plan* pl, sfs2d_window* out_host, int64_t cap, in
   if (pl->null_nrec && !out_host) return SFS2D_E_ARG;
   if (pl->null_nrec)
     HIPCHK(ctx, hipMemcpyAsync(out_host, pl->null_last, sizeof(sfs2d_window) * (size_t)pl->null_nrec, hipMemcpyDeviceToHost,
+                               CTX_STREAM(ctx)));
+  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------ diversity
+
+int sfs2d_plan_diversity(sfs2d_plan* pl, sfs2d_diversity* out_dev) {
+  if (!pl) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  const sfs2d_data* d = pl->data;
+  if (pl->runs == 0)
+    return set_err(ctx, SFS2D_E_ARG, pl->base ? "diversity before the base plan's first run (an attached plan has no records yet)"
+                                              : "diversity before the plan's first run (no records yet)");
+  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "diversity: data set too large for 32-bit SNP indices");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (!out_dev && !pl->d_div && pl->nrec) {
+    int rc = dalloc(ctx, &pl->d_div, (size_t)pl->nrec);
+    if (rc) return rc;
+  }
+  sfs2d_diversity* out = out_dev ? out_dev : pl->d_div;
+  pl->div_last = out;
+  pl->div_nrec = pl->nrec;
+  if (pl->nrec == 0) return 0;
+  const sfs2d_window* recs = pl->last_out ? pl->last_out : pl->d_out;
+  // one wavefront per record, four per workgroup, the records strided over at most 2048 workgroups (as k_fst_win)
+  const uint32_t nrec = (uint32_t)pl->nrec;
+  const dim3 g((unsigned)std::min<uint32_t>(2048u, (nrec + 3u) / 4u));
+  const double2* rt = reinterpret_cast<const double2*>(ctx->d_df + 2 * LNT);
+  if (pl->cnt)
+    hipLaunchKernelGGL(k_div_win<true>, g, dim3(DIV_BLOCK), 0, CTX_STREAM(ctx), pl->K, d->counts, scan_src(pl), recs, rt,
+                       ctx->d_hw, out, nrec, (uint32_t)d->n);
+  else
+    hipLaunchKernelGGL(k_div_win<false>, g, dim3(DIV_BLOCK), 0, CTX_STREAM(ctx), pl->K, d->counts, scan_src(pl), recs, rt,
+                       ctx->d_hw, out, nrec, (uint32_t)d->n);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int sfs2d_plan_diversity_read(sfs2d_plan* pl, sfs2d_diversity* out_host, int64_t cap, int64_t* nrec_out) {
+  if (!pl || !nrec_out) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  if (pl->div_nrec < 0) return set_err(ctx, SFS2D_E_ARG, "sfs2d_plan_diversity_read before sfs2d_plan_diversity");
+  *nrec_out = pl->div_nrec;
+  if (cap < pl->div_nrec) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
+  if (pl->div_nrec && !out_host) return SFS2D_E_ARG;
+  if (pl->div_nrec)
+    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->div_last, sizeof(sfs2d_diversity) * (size_t)pl->div_nrec, hipMemcpyDeviceToHost,
                                CTX_STREAM(ctx)));
   HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
   return 0;

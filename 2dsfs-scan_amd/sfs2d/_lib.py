@@ -45,6 +45,7 @@ EXPORTS = [
     "sfs2d_plan_create_sliding", "sfs2d_plan_attach_sliding", "sfs2d_plan_null_run", "sfs2d_plan_null_read",
     "sfs2d_plan_null_run_blocks",
     "sfs2d_plan_scan_variant", "sfs2d_plan_seg_kind", "sfs2d_plan_slots_once",
+    "sfs2d_plan_diversity", "sfs2d_plan_diversity_read",
 ]
 ABI_VERSION = 2   # SFS2D_ABI_VERSION of include/sfs2d.h
 
@@ -79,6 +80,14 @@ WINDOW_DTYPE = np.dtype([
     ("t2d", "<f8"), ("t1d_p1", "<f8"), ("t1d_p2", "<f8"),
 ])
 assert WINDOW_DTYPE.itemsize == 64
+
+# sfs2d_diversity: per-window sums, one per window record at the same index (sfs2d_plan_diversity)
+DIVERSITY_DTYPE = np.dtype([
+    ("pi1", "<f8"), ("pi2", "<f8"), ("dxy", "<f8"), ("thw1", "<f8"), ("thw2", "<f8"),
+    ("ar1_full", "<u8"), ("ar2_full", "<u8"),
+    ("s1", "<u4"), ("s2", "<u4"), ("s1_full", "<u4"), ("s2_full", "<u4"), ("flags", "<u4"), ("reserved", "<u4"),
+])
+assert DIVERSITY_DTYPE.itemsize == 80
 
 _lib = None
 
@@ -154,6 +163,8 @@ def lib():
     L.sfs2d_plan_null_run.argtypes = [vp, C.POINTER(NullParams), vp, i64, vp]
     L.sfs2d_plan_null_run_blocks.argtypes = [vp, C.POINTER(NullParams), i64, vp, i64, vp]
     L.sfs2d_plan_null_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.sfs2d_plan_diversity.argtypes = [vp, vp]
+    L.sfs2d_plan_diversity_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sfs2d_data_synth_sims.argtypes = [vp, C.POINTER(SynthParams), vp, vp, i32, vp, i32, C.POINTER(vp)]
     L.sfs2d_data_read.argtypes = [vp, vp, vp, i64]
     L.sfs2d_ctx_use_own_stream.argtypes = [vp]

@@ -22,6 +22,9 @@ multi_sliding_scan): ``<prefix>_20kb_step5kb.csv`` with the same columns, clean 
 ``--null-replicates R [--null-seed S] [--null-sizes exact]`` appends six bootstrap p-value columns
 (``p_T2D`` ... ``p_T2D_diff``, after ``FST`` when present) to every output file: R windows of the same
 SNP count drawn from the window's chromosome per size class (scan_pvalues).
+``--diversity`` appends twelve columns (``pi_pop1`` ... ``tajima_d_pop2``: per-site pi, dxy, da and Watterson's
+theta, segregating sites, Tajima's D; sfs2d.diversity) after ``FST`` when present and before
+the ``p_*`` columns, summed on the GPU over the data the scan already holds.
 ``--null-block B|window`` (with ``--null-replicates``) draws runs of B consecutive SNPs instead of single
 SNPs, so that the null keeps the chromosome's linkage; ``window``: one run as long as the window.
 """
@@ -53,11 +56,14 @@ def read_pixy_fst(path):
 P_COLS = ["p_T2D", "p_T1D_pop1", "p_T1D_pop2", "p_new_term_pop1", "p_new_term_pop2", "p_T2D_diff"]
 
 
-def write_csv(path, stats, chr_ids, fst=None, pixy=None, pvalues=False):
-    """save_csv_stats (twoDSFS_class.py:1884-1907) + optional FST column + optional p-value columns
-    (the rows' p_* keys, scan_pvalues)."""
+def write_csv(path, stats, chr_ids, fst=None, pixy=None, pvalues=False, diversity=False):
+    """save_csv_stats (twoDSFS_class.py:1884-1907) + optional FST column + optional diversity columns (the rows'
+    sfs2d.diversity.KEYS, after FST) + optional p-value columns (the rows' p_* keys, scan_pvalues).  A None is
+    an empty field, as for the statistics."""
     import twoDSFS_class as T
-    cols = list(T.col_names) + (["FST"] if (fst is not None or pixy is not None) else []) + (P_COLS if pvalues else [])
+    from .diversity import KEYS as D_COLS
+    cols = (list(T.col_names) + (["FST"] if (fst is not None or pixy is not None) else []) + (D_COLS if diversity else [])
+            + (P_COLS if pvalues else []))
     with open(path, "w", newline="") as fh:
         w = csv.DictWriter(fh, fieldnames=cols)
         w.writeheader()
@@ -72,6 +78,9 @@ def write_csv(path, stats, chr_ids, fst=None, pixy=None, pvalues=False):
                 row["FST"] = fst.get(label)
             elif pixy is not None:
                 row["FST"] = pixy.get((chrom, s, e))
+            if diversity:
+                for c in D_COLS:
+                    row[c] = r.get(c)
             if pvalues:
                 for c in P_COLS:
                     row[c] = r.get(c)
@@ -103,6 +112,8 @@ def main(argv=None):
     ap.add_argument("--null-block", default=None, metavar="B|window",
                     help="resample runs of B consecutive SNPs (window: one run per replicate window) instead of "
                          "single SNPs; needs --null-replicates")
+    ap.add_argument("--diversity", action="store_true",
+                    help="append per-window pi, dxy, da, Watterson's theta, S and Tajima's D (twelve columns)")
     ap.add_argument("--out-prefix", default="stats")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="VCF parser threads (0 = all)")
@@ -126,6 +137,7 @@ def main(argv=None):
             if not 1 <= block < (1 << 32):
                 ap.error("--null-block must be an integer in [1, 2^32) or 'window'")
     nkw = dict(replicates=a.null_replicates, seed=a.null_seed, sizes=a.null_sizes, block=block)
+    dkw = dict(diversity=True) if a.diversity else {}   # (without the flag every call is the one it was)
     if a.step is not None:
         if a.snp_window:
             ap.error("--step applies to fixed-bp windows: not with --snp-window")
@@ -153,35 +165,35 @@ def main(argv=None):
     t = time.perf_counter()
     if a.step is not None:   # sliding windows: every size from one upload and one k_prep pass
         if null:
-            res = obj.scan_pvalues(packed, a.window, step_size=a.step, fst=a.fst, **nkw)
+            res = obj.scan_pvalues(packed, a.window, step_size=a.step, fst=a.fst, **nkw, **dkw)
         else:
-            res = obj.multi_sliding_scan(packed, a.window, a.step, fst=a.fst)
+            res = obj.multi_sliding_scan(packed, a.window, a.step, fst=a.fst, **dkw)
         print(f"multi_sliding_scan ({len(a.window)} window sizes, step {a.step}): {time.perf_counter() - t:.2f} s",
               file=sys.stderr)
         for ws in a.window:
             path = f"{a.out_prefix}_{_fmt_kb(ws)}_step{_fmt_kb(a.step)}.csv"
             rows = res[ws]
-            write_csv(path, rows, chr_ids, {k: r["FST"] for k, r in rows.items()} if a.fst else None, pixy, null)
+            write_csv(path, rows, chr_ids, {k: r["FST"] for k, r in rows.items()} if a.fst else None, pixy, null, **dkw)
             outs.append(path)
             print(f"sliding_scan {ws} bp / {a.step} bp: {len(rows)} windows -> {path}", file=sys.stderr)
         return outs
     # every window size from one k_prep pass over the resident stream (sfs2d_plan_attach)
     if null:
-        res = obj.scan_pvalues(packed, a.window, a.snp_window, fst=a.fst, **nkw)
+        res = obj.scan_pvalues(packed, a.window, a.snp_window, fst=a.fst, **nkw, **dkw)
     else:
-        res = obj.multi_scan(packed, a.window, a.snp_window, fst=a.fst)
+        res = obj.multi_scan(packed, a.window, a.snp_window, fst=a.fst, **dkw)
     print(f"multi_scan ({len(a.window)} bp + {len(a.snp_window)} SNP-count window sizes): "
           f"{time.perf_counter() - t:.2f} s", file=sys.stderr)
     for ws in a.window:
         path = f"{a.out_prefix}_{_fmt_kb(ws)}.csv"
-        write_csv(path, res[ws], chr_ids, res["fst"][ws] if a.fst else None, pixy, null)
+        write_csv(path, res[ws], chr_ids, res["fst"][ws] if a.fst else None, pixy, null, **dkw)
         outs.append(path)
         print(f"combined_scan {ws} bp: {len(res[ws])} windows -> {path}", file=sys.stderr)
     for S in a.snp_window:
         stats = res[f"{S}snps"]
         fst = obj.window_fst(packed, snp_window_size=S) if a.fst else None
         path = f"{a.out_prefix}_{S}snps.csv"
-        write_csv(path, stats, chr_ids, fst, pixy, null)
+        write_csv(path, stats, chr_ids, fst, pixy, null, **dkw)
         outs.append(path)
         print(f"scan_perChr_bySNPs {S} SNPs: {len(stats)} windows -> {path}", file=sys.stderr)
     return outs

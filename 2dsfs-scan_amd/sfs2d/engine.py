@@ -333,6 +333,21 @@ class Plan:
             raise ValueError("null_read before null_run")
         return np.concatenate(parts) if parts else self._null_read_call()
 
+    def diversity(self, out_dev_ptr: Optional[int] = None) -> Optional[np.ndarray]:
+        """The diversity sums of this plan's last run (sfs2d_plan_diversity): one DIVERSITY_DTYPE record per
+        window record, at the same index (pi, dxy, Watterson's theta and the inputs of Tajima's D as sums over the
+        window; sfs2d.diversity.rows makes the per-site columns).  Any plan that has run, attached plans included.
+        With ``out_dev_ptr`` (a device buffer of ``nrec`` records) nothing is copied to the host and None is
+        returned."""
+        self.eng.check(self.eng.lib.sfs2d_plan_diversity(self.h, C.c_void_p(out_dev_ptr) if out_dev_ptr else None))
+        if out_dev_ptr:
+            return None
+        out = np.zeros(self.nrec, dtype=L.DIVERSITY_DTYPE)
+        n = C.c_int64()
+        self.eng.check(self.eng.lib.sfs2d_plan_diversity_read(self.h, L.ptr(out) if self.nrec else None, self.nrec,
+                                                              C.byref(n)))
+        return out
+
     def bg_buffer(self):
         p = C.c_void_p()
         nb = C.c_int64()

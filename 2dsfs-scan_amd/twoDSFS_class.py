@@ -270,18 +270,30 @@ class LikelihoodInference_jointSFS:
         return post.single_stat_scan(recs, q, window_size, post.num_slots(recs), 2, "T2D")
 
     # ------------------------------------------------------------------ multi-resolution (extension)
-    def multi_scan(self, data_dict, window_sizes=(), snp_window_sizes=(), fst=False):
+    def multi_scan(self, data_dict, window_sizes=(), snp_window_sizes=(), fst=False, diversity=False):
         """combined_scan at every size in ``window_sizes`` and scan_perChr_bySNPs at every size in
         ``snp_window_sizes`` from ONE pass over the SNP stream (the reference script runs these
         scans one after another over the same data, twoDSFS_class.py:1923-2032): the smallest
         fixed-bp scan is the base plan, the others are attached to it (sfs2d_plan_attach).
         Returns {ws: combined_scan result, "<S>snps": scan_perChr_bySNPs result}, plus
-        {"fst": {ws: window_fst result}} when ``fst`` (fixed-bp windows only)."""
-        return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst)
+        {"fst": {ws: window_fst result}} when ``fst`` (fixed-bp windows only).  ``diversity``: every row
+        also holds the twelve columns of ``window_diversity`` (sfs2d.diversity.KEYS), summed on the GPU over
+        the same resident data (k_div_win after the run)."""
+        return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, diversity=diversity)
 
-    def _multi_scan(self, data_dict, window_sizes, snp_window_sizes, fst, after_run=None):
+    def _no_distributed_diversity(self, diversity):
+        if diversity and self.distributed:
+            raise NotImplementedError("diversity is single-GPU (distributed sharding of the diversity sums is not implemented)")
+
+    def _add_diversity(self, rows, recs, pl, p, kind, w, step=None):
+        """The twelve diversity columns into ``rows`` (the result rows of plan ``pl``'s records ``recs``)."""
+        from sfs2d import diversity as DV
+        DV.add_columns(rows, recs, pl.diversity(), p, w, kind, step, (self.pop1_size, self.pop2_size))
+
+    def _multi_scan(self, data_dict, window_sizes, snp_window_sizes, fst, after_run=None, diversity=False):
         """multi_scan; ``after_run(p, base plan, [(recs, record labels, rows)])`` is called while the
         plans are alive (scan_pvalues adds its columns there)."""
+        self._no_distributed_diversity(diversity)
         p = self._pack(data_dict)
         bps = sorted(set(int(w) for w in window_sizes))
         snps = [int(x) for x in dict.fromkeys(snp_window_sizes)]
@@ -323,6 +335,8 @@ class LikelihoodInference_jointSFS:
                             out.setdefault("fst", {})[w] = post.window_fst_labels(recs, pl.read_fst(), p, w, True)
                     else:
                         out[f"{w}snps"] = post.bysnp_scan(recs, p, w, with_diff=True, final_warning=False)
+                    if diversity:
+                        self._add_diversity(out[w if kind == "bp" else f"{w}snps"], recs, pl, p, kind, w)
                     if after_run is not None:
                         items.append((recs, post.record_labels(recs, p, kind, w), out[w if kind == "bp" else f"{w}snps"]))
                 if after_run is not None:
@@ -351,14 +365,16 @@ class LikelihoodInference_jointSFS:
                 raise ValueError(f"window size {w} is more than 64 steps of {step}")
         return step
 
-    def sliding_scan(self, data_dict, window_size, step_size, background_chromosome=None, fst=False):
+    def sliding_scan(self, data_dict, window_size, step_size, background_chromosome=None, fst=False, diversity=False):
         """Overlapping fixed-bp windows: ``window_size`` bp advanced by ``step_size`` bp (a divisor of the
         window, at most 64 steps per window; sfs2d_plan_create_sliding).  The reference has no such scan:
         its script scans at 20 kb and at 500 kb and compares (twoDSFS_class.py:1923-1932) because a signal on
         an edge of its disjoint windows is split between two of them.  ``background_chromosome`` None: each
         chromosome is its own background (as combined_scan); else that chromosome's SFS for every window (as
         scan_chooseChr).  Returns {"<chrom> <start>-<end>": row} per non-empty window with combined_scan's
-        seven keys, plus "FST" (Hudson's, as window_fst) when ``fst``; clean None rules (post.sliding_scan)."""
+        seven keys, plus "FST" (Hudson's, as window_fst) when ``fst`` and the twelve diversity columns
+        (``window_diversity``) when ``diversity``; clean None rules (post.sliding_scan)."""
+        self._no_distributed_diversity(diversity)
         if self.distributed:
             raise NotImplementedError("sliding_scan is single-GPU (distributed sharding of sliding windows is not implemented)")
         ws = int(window_size)
@@ -382,21 +398,25 @@ class LikelihoodInference_jointSFS:
                 pl.check()
                 recs = pl.read()
                 f = pl.read_fst() if fst else None
+                rows = post.sliding_scan(recs, p, ws, step, f)
+                if diversity:
+                    self._add_diversity(rows, recs, pl, p, "bp", ws, step)
             finally:
                 pl.close()
         finally:
             dev.close()
-        return post.sliding_scan(recs, p, ws, step, f)
+        return rows
 
-    def multi_sliding_scan(self, data_dict, window_sizes, step_size, fst=False):
+    def multi_sliding_scan(self, data_dict, window_sizes, step_size, fst=False, diversity=False):
         """sliding_scan (per-chromosome backgrounds) at every size in ``window_sizes`` with one step, from
         ONE upload and one k_prep pass: the smallest window is a sliding plan of its own, the others are
         attached to it (sfs2d_plan_attach_sliding).  Returns {window_size: sliding_scan rows}.  A window the
-        step does not divide raises ValueError before any GPU work."""
-        return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst)
+        step does not divide raises ValueError before any GPU work.  ``diversity``: as in multi_scan."""
+        return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, diversity=diversity)
 
-    def _multi_sliding_scan(self, data_dict, window_sizes, step_size, fst, after_run=None):
+    def _multi_sliding_scan(self, data_dict, window_sizes, step_size, fst, after_run=None, diversity=False):
         """multi_sliding_scan, with ``after_run`` as in _multi_scan."""
+        self._no_distributed_diversity(diversity)
         if self.distributed:
             raise NotImplementedError("multi_sliding_scan is single-GPU (distributed sharding of sliding windows is not implemented)")
         wss = sorted(set(int(w) for w in window_sizes))
@@ -421,6 +441,8 @@ class LikelihoodInference_jointSFS:
                     pl.check()
                     recs = pl.read()
                     out[w] = post.sliding_scan(recs, p, w, step, pl.read_fst() if fst else None)
+                    if diversity:
+                        self._add_diversity(out[w], recs, pl, p, "bp", w, step)
                     if after_run is not None:
                         items.append((recs, post.record_labels(recs, p, "bp", w, step), out[w]))
                 if after_run is not None:
@@ -485,7 +507,8 @@ class LikelihoodInference_jointSFS:
         return int(block)
 
     def scan_pvalues(self, data_dict, window_sizes=(), snp_window_sizes=(), step_size=None,
-                     background_chromosome=None, replicates=999, seed=0, sizes=None, fst=False, block=None):
+                     background_chromosome=None, replicates=999, seed=0, sizes=None, fst=False, block=None,
+                     diversity=False):
         """The scans of ``multi_scan`` (``step_size`` given: ``multi_sliding_scan``) with a bootstrap p-value
         beside every statistic: each row additionally holds p_T2D, p_T1D_pop1, p_T1D_pop2, p_new_term_pop1,
         p_new_term_pop2 and p_T2D_diff -- the share of ``replicates`` windows of the same number of SNPs
@@ -500,8 +523,10 @@ class LikelihoodInference_jointSFS:
         that many SNPs on the chromosome ("blocks").
         ``background_chromosome``: one window size, scanned as scan_chooseChr (or scan_chooseChr_bySNPs for a
         SNP-count size, sliding_scan with ``step_size``) does; that chromosome is every window's pool; the
-        result is {size: rows}.  Not in the reference (it thresholds by SNP-count quantile and top 1 % in R,
+        result is {size: rows}.  ``diversity``: every row also holds the twelve diversity columns
+        (``window_diversity``; they get no p-values).  Not in the reference (it thresholds by SNP-count quantile and top 1 % in R,
         ECBstats_plots.R:45-50, 147-219)."""
+        self._no_distributed_diversity(diversity)
         if self.distributed:
             raise NotImplementedError("scan_pvalues is single-GPU (distributed sharding of the null is not implemented)")
         if int(replicates) < 1:
@@ -514,10 +539,10 @@ class LikelihoodInference_jointSFS:
             return lambda p, base, items: self._null_columns(p, base, items, replicates, seed, sizes, pool, block)
         if background_chromosome is None:
             if step_size is None:
-                return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, hook())
+                return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, hook(), diversity=diversity)
             if len(tuple(snp_window_sizes)):
                 raise ValueError("step_size applies to fixed-bp windows: not with snp_window_sizes")
-            return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, hook())
+            return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, hook(), diversity=diversity)
         # one chromosome as every window's background (and pool)
         bps, snps = [int(w) for w in window_sizes], [int(w) for w in snp_window_sizes]
         if len(bps) + len(snps) != 1:
@@ -553,6 +578,8 @@ class LikelihoodInference_jointSFS:
                 else:
                     rows = post.fixed_bg_scan(recs, p, w, post.num_slots(recs))
                 labels = post.record_labels(recs, p, "snps" if snps else "bp", w, step)
+                if diversity:
+                    self._add_diversity(rows, recs, pl, p, "snps" if snps else "bp", w, step)
                 self._null_columns(p, pl, [(recs, labels, rows)], replicates, seed, sizes, pool=bgc, block=block)
             finally:
                 pl.close()
@@ -585,6 +612,43 @@ class LikelihoodInference_jointSFS:
         finally:
             dev.close()
         return post.window_fst_labels(recs, fst, p, int(window_size if bp else snp_window_size), bp)
+
+    # ------------------------------------------------------------------ diversity (extension)
+    def window_diversity(self, data_dict, window_size=None, snp_window_size=None, step_size=None):
+        """What kind of window a T2D / Fst peak is: per window {label: {pi_pop1, pi_pop2, dxy, da, theta_w_pop1,
+        theta_w_pop2, S_pop1, S_pop2, S_full_pop1, S_full_pop2, tajima_d_pop1, tajima_d_pop2}}, labels as
+        combined_scan (``window_size``; sliding_scan with ``step_size``) or scan_perChr_bySNPs
+        (``snp_window_size``) emit them.  Not in the reference (its users join pixy's or scikit-allel's columns
+        by window label).  The sums are taken on the GPU over the SNPs of each window's 2D SFS (k_div_win;
+        DESIGN.md section 15, sfs2d.diversity): pi, dxy, da = dxy - (pi1 + pi2) / 2 and Watterson's theta are
+        per site -- divided by the window size in bp (every site of a fixed-bp window is taken as callable: a
+        SNP-only VCF knows nothing else) or, for SNP-count windows, by last position - first position + 1; S is
+        the number of segregating sites; Tajima's D rests on the S_full SNPs that are fully called in the
+        population (D is defined for one sample size) and is None without any, or for fewer than 2 individuals."""
+        self._no_distributed_diversity(True)
+        p = self._pack(data_dict)
+        if (window_size is None) == (snp_window_size is None):
+            raise ValueError("give exactly one of window_size / snp_window_size")
+        bp = window_size is not None
+        if step_size is not None and not bp:
+            raise ValueError("step_size applies to fixed-bp windows: not with snp_window_size")
+        w = int(window_size if bp else snp_window_size)
+        step = None if step_size is None else self._check_steps([w], step_size)
+        cfg = self._cfg(p, window_mode=L.WINDOW_BP if bp else L.WINDOW_SNPS, window=w, bg_mode=L.BG_PER_CHROM, step=step)
+        from sfs2d import diversity as DV
+        eng = self._engine()
+        dev = eng.upload(p)
+        try:
+            pl = eng.plan(dev, cfg)
+            try:
+                pl.run()
+                pl.check()
+                recs, div = pl.read(), pl.diversity()
+            finally:
+                pl.close()
+        finally:
+            dev.close()
+        return DV.rows(recs, div, p, w, "bp" if bp else "snps", step, (self.pop1_size, self.pop2_size))
 
     # ------------------------------------------------------------------ SFS primitives
     def calculate_2d_sfs(self, data_dict):

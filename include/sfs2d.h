@@ -39,7 +39,7 @@ extern "C" {
  * sfs2d_graph_* added (round 6, additive); sfs2d_plan_create_sliding / sfs2d_plan_attach_sliding added
  * (additive: sfs2d_params keeps its layout, the step is an argument); sfs2d_plan_null_run / _null_read added
  * (additive); sfs2d_plan_null_run_blocks added (additive: sfs2d_null_params keeps its layout, the block length is
- * an argument) */
+ * an argument); sfs2d_plan_diversity / _diversity_read and sfs2d_diversity added (additive) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -311,6 +311,36 @@ int sfs2d_plan_null_run(sfs2d_plan* plan, const sfs2d_null_params* np, const int
 int sfs2d_plan_null_run_blocks(sfs2d_plan* plan, const sfs2d_null_params* np, int64_t block, const int64_t* tasks,
                                int64_t ntasks, sfs2d_window* out_dev);
 int sfs2d_plan_null_read(sfs2d_plan* plan, sfs2d_window* out_host, int64_t cap, int64_t* nrec_out);
+/* Per-window diversity: what kind of window a T2D / Fst peak is.  One record per record of
+ * the plan's last run, at the same index; every field is a SUM over the window's SNPs (per-site values are the
+ * caller's: sfs2d/diversity.py divides by the window length).  The SNPs are those of the record's own range
+ * [begin, end) that are in the window's 2D SFS (the plan's position / variant_type filters, the joint fold); the
+ * SNPs the SFS drops as bin (0, 0) are fixed for one allele in both populations and add exactly 0 to every field.
+ * Per SNP, population k with counts (r, a), n = r + a called alleles:
+ *   pi_k   += 2 a r / (n (n - 1))        (n >= 2; a fixed site adds exactly 0.0)
+ *   s_k    += 1 when 0 < a < n           (segregating in k)
+ *   thw_k  += [0 < a < n] / h(n),  h(n) = sum_{i=1}^{n-1} 1 / i      (Watterson, per SNP's own sample size)
+ *   dxy    += (a1 r2 + r1 a2) / (n1 n2)  (n1, n2 >= 1)
+ *   s_k_full, ar_k_full: s_k and the integer a r over the SNPs FULLY called in k (n == 2 pop_size_k exactly; a SNP
+ *   with missing or surplus calls is not): Tajima's D is defined for one sample size, so it is formed from these
+ *   (n = 2 pop_size_k, S = s_k_full, pi = 2 ar_k_full / (n (n - 1))) on the host.
+ * flags: SFS2D_W_EMPTY / SFS2D_W_EXTRA of the source record; such a record has every other field 0.
+ * The first member is a double (sfs2d_window is the record struct that begins with a uint32_t). */
+typedef struct {
+  double pi1, pi2, dxy, thw1, thw2;
+  uint64_t ar1_full, ar2_full;
+  uint32_t s1, s2, s1_full, s2_full, flags, reserved;
+} sfs2d_diversity;
+/* enqueue the diversity sums of the plan's last run (its records: sfs2d_plan_run's out_dev or the plan's own) on
+ * the ctx stream; out_dev: device buffer of sfs2d_plan_num_records records (NULL = plan-owned, read with
+ * sfs2d_plan_diversity_read).  Any plan that has run, attached plans included (their own records, their base's
+ * data); reads the records, the counts and (filtered plans) the per-SNP bins, writes out_dev alone: a following
+ * run or null run finds everything as it was.  SFS2D_E_ARG, with the reason in sfs2d_last_error: a plan that
+ * has not run.  The reference has no such statistic (its users join pixy's or scikit-allel's by window label). */
+int sfs2d_plan_diversity(sfs2d_plan* plan, sfs2d_diversity* out_dev);
+/* copy the last sfs2d_plan_diversity call's records to host (synchronises); SFS2D_E_CAP: cap below the record
+ * count (*nrec_out holds it); SFS2D_E_ARG: no diversity call since the plan was created */
+int sfs2d_plan_diversity_read(sfs2d_plan* plan, sfs2d_diversity* out_host, int64_t cap, int64_t* nrec_out);
 /* launch geometry (threads per grid) of k_prep and of the scan kernel: matches the Grid_Size column
  * of rocprofv3 kernel traces, so profiles can be joined to a plan */
 int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* scan_threads);
