@@ -164,6 +164,9 @@ struct sfs2d_plan {
   bool slots_once = false, slots_written = false;
   int64_t step = 0;         // sliding plan: fixed-bp windows advanced by step bp (0: disjoint windows); its
                             // slots by k_slots_slide, k_prep without segmentation
+  bool regions = false;     // regions plan: slot s is the caller's interval s (d_reg), its slots by k_slots_regions
+                            // where a sliding plan launches k_slots_slide; everything else as a sliding plan
+  uint2* d_reg = nullptr;   // the regions' (first, last), 1-based inclusive, in slot order
   bool fused = false;       // per-chromosome tables built inside k_scan_w (parity-alternating replicas)
   bool sliced = false;      // per-chromosome tables by k_bg_slice without its tail; k_scan_w combines
                             // the leaf sums (parity-alternating inner sums)
@@ -291,7 +294,7 @@ void plan_free(sfs2d_plan* p) {
       p->d_tab = nullptr; p->d_lp = nullptr; p->d_head = nullptr;
     }
   }
-  hipFree(p->d_slot_base);
+  hipFree(p->d_slot_base); hipFree(p->d_reg);
   hipFree(p->d_tiles); hipFree(p->d_chunks); hipFree(p->d_slots); hipFree(p->d_repl); hipFree(p->d_bcount); hipFree(p->d_ctr);
   hipFree(p->d_done); hipFree(p->d_bgval); hipFree(p->d_tab); hipFree(p->d_lp); hipFree(p->d_head);
   hipFree(p->d_bg1d); hipFree(p->d_leafsum); hipFree(p->d_leaves); hipFree(p->d_nodes); hipFree(p->d_slices);
@@ -323,6 +326,10 @@ const uint32_t* scan_src(const sfs2d_plan* pl) { return pl->cnt ? pl->data->coun
 // k_prep sums Fst per window slot (fixed point, d_fsum) and the scan takes the sums: Fst is asked for, and
 // neither window kernels (fst_win) nor the scan itself (fst_scan) compute it
 bool prep_sums_fst(const sfs2d_plan* pl) { return pl->fst && !pl->fst_win && !pl->fst_scan; }
+
+// sliding and regions plans: windows that may overlap, so k_prep does not segment for them (nor sum Fst per
+// window); their slot kernel runs after k_prep and their Fst is the scan's or k_fst_win's
+bool free_slots(const sfs2d_plan* pl) { return pl->step > 0 || pl->regions; }
 
 struct ScanW {   // k_scan_w<P16, FUSED, FST, CNT, GATE, LEAN>
   bool p16, fused;
@@ -590,14 +597,19 @@ hipError_t stage_slots(sfs2d_plan* pl) {
   return e;
 }
 
-// a sliding plan's slot table (after k_prep, which does not segment for it).  ev: with the k_prep timing
-// events, when the run launches no k_prep (this is then its segmentation stage, as launch_slots_only)
+// a sliding or regions plan's slot table (after k_prep, which does not segment for it).  ev: with the k_prep
+// timing events, when the run launches no k_prep (this is then its segmentation stage, as launch_slots_only)
 hipError_t launch_slots_slide(sfs2d_plan* pl, bool ev) {
   const uint32_t ns = (uint32_t)pl->nslots;
   if (!ns) return hipSuccess;
-  hipExtLaunchKernelGGL(k_slots_slide, dim3((ns + 255u) / 256u), dim3(256), 0, CTX_STREAM(pl->ctx), ev ? pl->kev[0] : nullptr,
-                        ev ? pl->kev[1] : nullptr, 0, pl->data->pos, pl->data->d_chrom_off, pl->d_slot_base, pl->data->nchrom,
-                        (uint32_t)pl->prm.window, (uint32_t)pl->step, ns, pl->d_slots);
+  if (pl->regions)
+    hipExtLaunchKernelGGL(k_slots_regions, dim3((ns + 255u) / 256u), dim3(256), 0, CTX_STREAM(pl->ctx), ev ? pl->kev[0] : nullptr,
+                          ev ? pl->kev[1] : nullptr, 0, pl->data->pos, pl->data->d_chrom_off, pl->d_slot_base, pl->data->nchrom,
+                          pl->d_reg, ns, pl->d_slots);
+  else
+    hipExtLaunchKernelGGL(k_slots_slide, dim3((ns + 255u) / 256u), dim3(256), 0, CTX_STREAM(pl->ctx), ev ? pl->kev[0] : nullptr,
+                          ev ? pl->kev[1] : nullptr, 0, pl->data->pos, pl->data->d_chrom_off, pl->d_slot_base, pl->data->nchrom,
+                          (uint32_t)pl->prm.window, (uint32_t)pl->step, ns, pl->d_slots);
   return hipGetLastError();
 }
 
@@ -655,7 +667,10 @@ int launch_attached(sfs2d_plan* a) {
   const uint32_t ns = (uint32_t)a->nslots;
   if (!ns) { a->runs++; return 0; }
   const dim3 g((ns + 255) / 256);
-  if (a->step)
+  if (a->regions)
+    hipLaunchKernelGGL(k_slots_regions, g, dim3(256), 0, CTX_STREAM(a->ctx), d->pos, d->d_chrom_off, a->d_slot_base,
+                       d->nchrom, a->d_reg, ns, a->d_slots);
+  else if (a->step)
     hipLaunchKernelGGL(k_slots_slide, g, dim3(256), 0, CTX_STREAM(a->ctx), d->pos, d->d_chrom_off, a->d_slot_base,
                        d->nchrom, (uint32_t)a->prm.window, (uint32_t)a->step, ns, a->d_slots);
   else if (a->prm.window_mode == SFS2D_WINDOW_BP)
@@ -1060,11 +1075,18 @@ struct Knobs {
   const char* jnt = std::getenv("SFS2D_JNT");                // 0 / 1: k_prep's joint histogram never / whatever the tile size
 };
 
+// a regions plan's intervals (host arrays, grouped by chromosome; checked by check_regions)
+struct RegionList {
+  const int32_t* chrom;
+  const uint32_t *first, *last;
+  int64_t n;
+};
+
 static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, int force_sliced, int64_t step,
-                       sfs2d_plan** out);
+                       const RegionList* rg, sfs2d_plan** out);
 
 int sfs2d_plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, sfs2d_plan** out) {
-  return plan_create(ctx, data, prm, -1, 0, out);
+  return plan_create(ctx, data, prm, -1, 0, nullptr, out);
 }
 
 // a sliding plan's step against its params (after make_kparams accepted them)
@@ -1086,13 +1108,51 @@ int sfs2d_plan_create_sliding(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2
   int rc = make_kparams(ctx, prm, data->nchrom, &K);
   if (!rc) rc = check_step(ctx, prm, step);
   // step == window is the disjoint geometry: the ordinary plan itself (records and Fst byte-equal by construction)
-  return rc ? rc : plan_create(ctx, data, prm, -1, step == prm->window ? 0 : step, out);
+  return rc ? rc : plan_create(ctx, data, prm, -1, step == prm->window ? 0 : step, nullptr, out);
+}
+
+// a regions plan's params and list (after make_kparams accepted the params); *longest: the longest region in bp,
+// what the plan's copy of params->window holds (2^32 - 1 for the one length above it, first = 0 .. last = 2^32 - 1)
+static int check_regions(sfs2d_ctx* ctx, const sfs2d_params* prm, int nchrom, const RegionList& rg, int64_t* longest) {
+  if (prm->window_mode != SFS2D_WINDOW_BP) return set_err(ctx, SFS2D_E_ARG, "regions are intervals in bp (SFS2D_WINDOW_BP), not SNP-count windows");
+  if (prm->flags & SFS2D_F_PREV_EXTRA)
+    return set_err(ctx, SFS2D_E_ARG, "SFS2D_F_PREV_EXTRA (quirk Q9 of the disjoint window loop) is not defined for regions");
+  if (!rg.chrom || !rg.first || !rg.last) return set_err(ctx, SFS2D_E_ARG, "regions: null array");
+  if (rg.n < 1) return set_err(ctx, SFS2D_E_ARG, "regions: the list must hold at least one region");
+  if (rg.n >= 0x80000000ll) return set_err(ctx, SFS2D_E_ARG, "regions: the list must hold fewer than 2^31 regions");
+  int64_t lg = 1;
+  for (int64_t i = 0; i < rg.n; ++i) {
+    if (rg.chrom[i] < 0 || rg.chrom[i] >= nchrom)
+      return set_err(ctx, SFS2D_E_ARG, "regions: chrom out of range at region " + std::to_string(i));
+    if (i && rg.chrom[i] < rg.chrom[i - 1])
+      return set_err(ctx, SFS2D_E_ARG, "regions: chrom decreases at region " + std::to_string(i) + " (group the list by chromosome)");
+    if (rg.first[i] > rg.last[i]) return set_err(ctx, SFS2D_E_ARG, "regions: first > last at region " + std::to_string(i));
+    lg = std::max<int64_t>(lg, (int64_t)rg.last[i] - (int64_t)rg.first[i] + 1);
+  }
+  *longest = std::min<int64_t>(lg, 0xffffffffll);
+  return 0;
+}
+
+// Regions: the windows are a caller's list of intervals (include/sfs2d.h).  The plan is built as a sliding plan is
+// (k_prep without segmentation, a slot kernel of its own after it, Fst by the scan or k_fst_win), with the list
+// as its slot table's source.
+int sfs2d_plan_create_regions(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, const int32_t* chrom,
+                              const uint32_t* first, const uint32_t* last, int64_t n, sfs2d_plan** out) {
+  if (!ctx || !data || !prm || !out) return set_err(ctx, SFS2D_E_ARG, "null argument");
+  *out = nullptr;
+  KParams K;
+  int rc = make_kparams(ctx, prm, data->nchrom, &K);
+  const RegionList rg{chrom, first, last, n};
+  sfs2d_params p = *prm;
+  if (!rc) rc = check_regions(ctx, prm, data->nchrom, rg, &p.window);
+  return rc ? rc : plan_create(ctx, data, &p, -1, 0, &rg, out);
 }
 
 // force_sliced: -1 choose (windows per wave), 0 fused, 1 sliced (attached plans follow their base)
 // step: 0 disjoint windows; > 0 a sliding plan (checked by check_step)
+// rg: null, or a regions plan's list (checked by check_regions; step 0, prm->window the longest region)
 static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* prm, int force_sliced, int64_t step,
-                       sfs2d_plan** out) {
+                       const RegionList* rg, sfs2d_plan** out) {
   if (!ctx || !data || !prm || !out) return set_err(ctx, SFS2D_E_ARG, "null argument");
   *out = nullptr;
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1100,16 +1160,18 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   int rc = make_kparams(ctx, prm, data->nchrom, &K);
   if (rc) return rc;
   const Knobs env;
-  const bool slide = step > 0;
-  const int64_t adv = slide ? step : prm->window;   // bp from one window's start to the next's
+  // (slide: every rule below that holds for windows k_prep does not segment -- a regions plan follows them all)
+  const bool slide = step > 0 || rg;
+  const int64_t adv = step > 0 ? step : prm->window;   // bp from one window's start to the next's
   sfs2d_plan* pl = new sfs2d_plan();
   pl->ctx = ctx; pl->data = data; pl->prm = *prm; pl->K = K;
   // no SNP of the data set has more called alleles than 2 pop_size in either population (max_nc1 / max_nc2)
   const bool nc_ok = data->max_nc1 <= (uint32_t)K.n1 && data->max_nc2 <= (uint32_t)K.n2;
   pl->K.nc_ok = nc_ok ? 1 : 0;
   const bool bp = prm->window_mode == SFS2D_WINDOW_BP;
-  pl->step = slide ? step : 0;
-  pl->do_seg = bp && !slide;   // (a sliding plan's slots: k_slots_slide after k_prep)
+  pl->step = step > 0 ? step : 0;
+  pl->regions = rg != nullptr;
+  pl->do_seg = bp && !slide;   // (a sliding plan's slots: k_slots_slide after k_prep; a regions plan's: k_slots_regions)
   pl->do_bg = prm->bg_mode == SFS2D_BG_PER_CHROM;
   pl->nbg = pl->do_bg ? std::max(1, data->nchrom) : 1;
   const int nc = data->nchrom;
@@ -1118,10 +1180,16 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   std::vector<unsigned long long> slot_base(nc + 1, 0);
   uint32_t last_c = 0;
   bool any = false;
+  std::vector<int64_t> rcount(rg ? nc : 0, 0);   // regions per chromosome: a chromosome's slots, SNPs or none
+  if (rg)
+    for (int64_t i = 0; i < rg->n; ++i) rcount[rg->chrom[i]]++;
   for (int c = 0; c < nc; ++c) {
     const int64_t len = data->chrom_off[c + 1] - data->chrom_off[c];
-    int64_t ns = 0;
-    if (len > 0) {
+    int64_t ns = rg ? rcount[c] : 0;
+    if (len > 0 && rg) {
+      last_c = (uint32_t)c;
+      any = true;
+    } else if (len > 0) {
       // (sliding: slot j starts at j step + 1, the last one holds the chromosome's last SNP)
       if (bp) ns = (int64_t)(data->last_pos[c] ? (data->last_pos[c] - 1u) / (uint32_t)adv : 0u) + 1;
       else ns = len / prm->window;
@@ -1188,12 +1256,21 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   bool p16_ok;
   if (!bp) {
     p16_ok = prm->window <= 65535;
-  } else if (data->strict && prm->window <= 65535) {
+  } else if (!rg && data->strict && prm->window <= 65535) {
     p16_ok = true;   // unique positions: a window of ws bp holds at most ws SNPs
   } else if (!data->host_pos.empty() || data->n == 0) {
     // exact longest window run from the host copy of the positions
     int64_t longest = 0;
-    for (int c = 0; c < nc; ++c) {
+    // (regions: the SNP count of every region, by the definition k_slots_regions implements -- two searches each)
+    for (int64_t i = 0; rg && i < rg->n; ++i) {
+      const uint32_t* hp = data->host_pos.data();
+      const uint32_t* cb = hp + data->chrom_off[rg->chrom[i]];
+      const uint32_t* ce = hp + data->chrom_off[rg->chrom[i] + 1];
+      const uint32_t* b = std::lower_bound(cb, ce, rg->first[i]);
+      const uint32_t* e = std::upper_bound(b, ce, rg->last[i]);   // the first pos >= last + 1, without the + 1
+      longest = std::max<int64_t>(longest, e - b);
+    }
+    for (int c = 0; c < nc && !rg; ++c) {
       int64_t run = 0;
       uint32_t pw = 0xffffffffu;
       if (slide) {   // a bound: the most SNPs in any ws bp that start at an SNP (every sliding window lies in one)
@@ -1524,11 +1601,18 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   rc = rc ? rc : dalloc(ctx, &pl->d_err, 4);
   if (pl->fst) rc = rc ? rc : dalloc(ctx, &pl->d_fst, (size_t)pl->nslots + 1);
   pl->d_fst_own = pl->d_fst;
-  if ((pl->seg_search || pl->seg_index || slide) && !rc) {   // k_slots_search's / k_slots_index's / k_slots_slide's slot bases per chromosome (u32: nslots < 2^31)
+  if ((pl->seg_search || pl->seg_index || slide) && !rc) {   // k_slots_search's / k_slots_index's / k_slots_slide's / k_slots_regions's slot bases per chromosome (u32: nslots < 2^31)
     std::vector<uint32_t> sb(pl->slot_base_h.begin(), pl->slot_base_h.end());
     rc = dalloc(ctx, &pl->d_slot_base, sb.size());
     if (!rc && hipMemcpy(pl->d_slot_base, sb.data(), sizeof(uint32_t) * sb.size(), hipMemcpyHostToDevice) != hipSuccess)
       rc = set_err(ctx, SFS2D_E_HIP, "slot bases upload");
+  }
+  if (rg && !rc) {   // k_slots_regions's (first, last) per slot: copied once, the caller's arrays are not kept
+    std::vector<uint2> reg((size_t)rg->n);
+    for (int64_t i = 0; i < rg->n; ++i) reg[(size_t)i] = make_uint2(rg->first[i], rg->last[i]);
+    rc = dalloc(ctx, &pl->d_reg, reg.size());
+    if (!rc && hipMemcpy(pl->d_reg, reg.data(), sizeof(uint2) * reg.size(), hipMemcpyHostToDevice) != hipSuccess)
+      rc = set_err(ctx, SFS2D_E_HIP, "regions upload");
   }
   if (pl->fst) rc = rc ? rc : dalloc(ctx, &pl->d_fsum, 2 * ((size_t)pl->nslots + 1));
   if (rc) { plan_free(pl); delete pl; return rc; }
@@ -1617,7 +1701,7 @@ int sfs2d_plan_run_phase(sfs2d_plan* pl, int phase, sfs2d_window* out_dev) {
     } else {
       if (pl->seg_index) HIPCHK(ctx, stage_slots(pl));
       if ((rc = launch_prep(pl, true))) return rc;
-      const bool slots = pl->step && pl->nslots;   // a sliding plan's table, after k_prep
+      const bool slots = free_slots(pl) && pl->nslots;   // a sliding / regions plan's table, after k_prep
       if (slots) HIPCHK(ctx, launch_slots_slide(pl, !prep_runs(pl)));
       if (!prep_runs(pl) && !slots && (rc = mark(0))) return rc;
     }
@@ -1625,7 +1709,7 @@ int sfs2d_plan_run_phase(sfs2d_plan* pl, int phase, sfs2d_window* out_dev) {
   if (phase == 0 || phase == 2) {
     if (pl->do_bg && !pl->fused) HIPCHK(ctx, launch_bg_slices(pl));
     else if ((rc = mark(2))) return rc;
-    if (pl->step && pl->fst_win) HIPCHK(ctx, launch_fst_win(pl));   // (the scan may clear the slots)
+    if (free_slots(pl) && pl->fst_win) HIPCHK(ctx, launch_fst_win(pl));   // (the scan may clear the slots)
     for (sfs2d_plan* a : pl->attached)   // before the base clears its state
       if ((rc = launch_attached(a))) return rc;
     sfs2d_window* out = out_dev ? out_dev : pl->d_out;
@@ -1655,6 +1739,7 @@ const char* sfs2d_plan_scan_kernel(const sfs2d_plan* pl) {
 
 const char* sfs2d_plan_seg_kind(const sfs2d_plan* pl) {
   if (!pl) return nullptr;
+  if (pl->regions) return "regions";
   if (pl->base) return pl->step ? "slide" : pl->prm.window_mode == SFS2D_WINDOW_BP ? "bp" : "none";
   if (pl->step) return "slide";
   if (pl->seg_index) return "index";
@@ -2268,10 +2353,10 @@ int sfs2d_plan_time(sfs2d_plan* pl, int iters, double* ms_run, double* ms_k1, do
     if (pl->seg_index) HIPCHK(ctx, stage_slots(pl));
     if (slots_only(pl)) HIPCHK(ctx, launch_slots_only(pl));
     else if ((rc = launch_prep(pl, true))) return rc;
-    if (pl->step) HIPCHK(ctx, launch_slots_slide(pl, false));
+    if (free_slots(pl)) HIPCHK(ctx, launch_slots_slide(pl, false));
     HIPCHK(ctx, hipEventRecord(pl->ev[1], st));
     if (pl->do_bg && !pl->fused) HIPCHK(ctx, launch_bg_slices(pl));
-    if (pl->step && pl->fst_win) HIPCHK(ctx, launch_fst_win(pl));
+    if (free_slots(pl) && pl->fst_win) HIPCHK(ctx, launch_fst_win(pl));
     for (sfs2d_plan* a : pl->attached)
       if ((rc = launch_attached(a))) return rc;
     HIPCHK(ctx, hipEventRecord(pl->ev[2], st));
@@ -2313,10 +2398,24 @@ int sfs2d_plan_destroy(sfs2d_plan* pl) {
   return 0;
 }
 
-static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, sfs2d_plan** out);
+static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, const RegionList* rg, sfs2d_plan** out);
 
 int sfs2d_plan_attach(sfs2d_plan* base, const sfs2d_params* prm, sfs2d_plan** out) {
-  return plan_attach(base, prm, 0, out);
+  return plan_attach(base, prm, 0, nullptr, out);
+}
+
+// a regions plan attached to an ordinary, sliding or regions base: the rules of an attached sliding plan
+int sfs2d_plan_attach_regions(sfs2d_plan* base, const sfs2d_params* prm, const int32_t* chrom, const uint32_t* first,
+                              const uint32_t* last, int64_t n, sfs2d_plan** out) {
+  if (!base || !prm || !out) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = base->ctx;
+  *out = nullptr;
+  KParams K;
+  int rc = make_kparams(ctx, prm, base->data->nchrom, &K);
+  const RegionList rg{chrom, first, last, n};
+  sfs2d_params p = *prm;
+  if (!rc) rc = check_regions(ctx, prm, base->data->nchrom, rg, &p.window);
+  return rc ? rc : plan_attach(base, &p, 0, &rg, out);
 }
 
 int sfs2d_plan_attach_sliding(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, sfs2d_plan** out) {
@@ -2329,12 +2428,12 @@ int sfs2d_plan_attach_sliding(sfs2d_plan* base, const sfs2d_params* prm, int64_t
   if (rc) return rc;
   // step == window is the disjoint geometry: the ordinary attached plan (byte-equal by construction), unless
   // it is refused for its Fst rule alone -- a sliding plan's Fst needs no sums of the base
-  if (step == prm->window && plan_attach(base, prm, 0, out) == 0) return 0;
-  return plan_attach(base, prm, step, out);
+  if (step == prm->window && plan_attach(base, prm, 0, nullptr, out) == 0) return 0;
+  return plan_attach(base, prm, step, nullptr, out);
 }
 
-// step: 0 an ordinary attached plan; > 0 a sliding one (checked by check_step)
-static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, sfs2d_plan** out) {
+// step: 0 an ordinary attached plan; > 0 a sliding one (checked by check_step); rg: a regions one (check_regions)
+static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, const RegionList* rg, sfs2d_plan** out) {
   if (!base || !prm || !out) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = base->ctx;
   *out = nullptr;
@@ -2349,7 +2448,7 @@ static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, 
     return set_err(ctx, SFS2D_E_ARG, "an attached plan may differ from its base only in the window and flags");
   const bool bp = prm->window_mode == SFS2D_WINDOW_BP;
   sfs2d_plan* a = nullptr;
-  int rc = plan_create(ctx, base->data, prm, base->sliced ? 1 : 0, step, &a);
+  int rc = plan_create(ctx, base->data, prm, base->sliced ? 1 : 0, step, rg, &a);
   if (rc) return rc;
   if (a->fused != base->fused || a->sliced != base->sliced || a->G != base->G || a->cnt != base->cnt) {
     plan_free(a); delete a;
@@ -2358,8 +2457,9 @@ static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, 
   // Fst of an attached plan: its own scan's sums (fst_scan), else the base's k_prep sums added per
   // attached window (fused bases) or k_fst_win on the attached slots (sliced bases)
   uint32_t m = 0;
-  // (a sliding attached plan: its own k_fst_win, whatever the base; a sliding base has no k_prep sums to add)
-  if ((prm->flags & SFS2D_F_FST) && !a->fst_scan && !step) {
+  // (a sliding or regions attached plan: its own k_fst_win, whatever the base; a sliding or regions base has no
+  // k_prep sums to add)
+  if ((prm->flags & SFS2D_F_FST) && !a->fst_scan && !step && !rg) {
     const bool base_bp = b.window_mode == SFS2D_WINDOW_BP;
     const char* why = nullptr;
     if (!bp) why = "attached Fst needs fixed-bp windows";
@@ -2388,7 +2488,7 @@ static int plan_attach(sfs2d_plan* base, const sfs2d_params* prm, int64_t step, 
   }
   a->base = base;
   a->fst_m = m;
-  a->fst_win = (base->sliced || step) && (prm->flags & SFS2D_F_FST) && !a->fst_scan;   // k_fst_win on the attached slots
+  a->fst_win = (base->sliced || step || rg) && (prm->flags & SFS2D_F_FST) && !a->fst_scan;   // k_fst_win on the attached slots
   a->nfst = 0;
   rc = 0;
   std::vector<uint32_t> sb(a->slot_base_h.begin(), a->slot_base_h.end());

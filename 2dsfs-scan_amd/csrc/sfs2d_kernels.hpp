@@ -3596,6 +3596,33 @@ __global__ __launch_bounds__(256) void k_slots_slide(const uint32_t* __restrict_
   slots[s] = b < e ? make_uint2(b + 1u, e) : make_uint2(0u, 0u);
 }
 
+// The slot table of a regions plan (sfs2d_plan_create_regions / _attach_regions): slot s is the caller's
+// region s, reg[s] = (first, last), 1-based inclusive positions on the chromosome the slot bases give it
+// (the list is grouped by chromosome).  begin = the chromosome's first SNP with pos >= first (first == 0
+// alone reaches a SNP at pos 0), end = the first with pos >= last + 1, in 64 bits (last = 2^32 - 1 is
+// legal); repeated positions at either boundary are all inside.  As k_slots_slide: one thread per slot, the
+// second search from the first's result, every slot written every run with one 8-B store, empty ones (also
+// every slot of a chromosome without SNPs: cb == ce) as (0, 0).  Regions overlap, nest and repeat freely:
+// no slot reads its neighbour.
+__global__ __launch_bounds__(256) void k_slots_regions(const uint32_t* __restrict__ pos, const long long* __restrict__ chrom_off,
+                                                       const uint32_t* __restrict__ slot_base, int nchrom,
+                                                       const uint2* __restrict__ reg, uint32_t nslots,
+                                                       uint2* __restrict__ slots) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= nslots) return;
+  const uint2 r = reg[s];    // (in flight during the chromosome search)
+  int lo = 0, hi = nchrom;   // chromosome c with slot_base[c] <= s < slot_base[c+1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (slot_base[mid] <= s) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t cb = (uint32_t)chrom_off[lo], ce = (uint32_t)chrom_off[lo + 1];
+  const uint32_t b = lower_bound_pos(pos, cb, ce, (unsigned long long)r.x);
+  const uint32_t e = lower_bound_pos(pos, b, ce, (unsigned long long)r.y + 1ull);
+  slots[s] = b < e ? make_uint2(b + 1u, e) : make_uint2(0u, 0u);
+}
+
 // Fst sums of an attached fixed-bp plan whose window is m times the base plan's: window j of
 // chromosome c is base windows [j*m, (j+1)*m) of c, and the base's int64 fixed-point sums add
 // exactly (the same value as k_prep accumulating the attached windows directly).

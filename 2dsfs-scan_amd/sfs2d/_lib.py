@@ -46,6 +46,7 @@ EXPORTS = [
     "sfs2d_plan_null_run_blocks",
     "sfs2d_plan_scan_variant", "sfs2d_plan_seg_kind", "sfs2d_plan_slots_once",
     "sfs2d_plan_diversity", "sfs2d_plan_diversity_read",
+    "sfs2d_plan_create_regions", "sfs2d_plan_attach_regions",
 ]
 ABI_VERSION = 2   # SFS2D_ABI_VERSION of include/sfs2d.h
 
@@ -160,6 +161,8 @@ def lib():
     L.sfs2d_plan_attach.argtypes = [vp, C.POINTER(Params), C.POINTER(vp)]
     L.sfs2d_plan_create_sliding.argtypes = [vp, vp, C.POINTER(Params), i64, C.POINTER(vp)]
     L.sfs2d_plan_attach_sliding.argtypes = [vp, C.POINTER(Params), i64, C.POINTER(vp)]
+    L.sfs2d_plan_create_regions.argtypes = [vp, vp, C.POINTER(Params), vp, vp, vp, i64, C.POINTER(vp)]
+    L.sfs2d_plan_attach_regions.argtypes = [vp, C.POINTER(Params), vp, vp, vp, i64, C.POINTER(vp)]
     L.sfs2d_plan_null_run.argtypes = [vp, C.POINTER(NullParams), vp, i64, vp]
     L.sfs2d_plan_null_run_blocks.argtypes = [vp, C.POINTER(NullParams), i64, vp, i64, vp]
     L.sfs2d_plan_null_read.argtypes = [vp, vp, i64, C.POINTER(i64)]

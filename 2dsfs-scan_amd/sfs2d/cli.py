@@ -27,6 +27,13 @@ theta, segregating sites, Tajima's D; sfs2d.diversity) aft
 the ``p_*`` columns, summed on the GPU over the data the scan already holds.
 ``--null-block B|window`` (with ``--null-replicates``) draws runs of B consecutive SNPs instead of single
 SNPs, so that the null keeps the chromosome's linkage; ``window``: one run as long as the window.
+
+``--regions FILE.bed`` scans the intervals of a BED file (genes, an inversion, candidate regions) as windows of
+their own, from the same pass as the ``--window`` scans when there are any (a regions plan attached to them), and
+writes ``<prefix>_regions.csv``: a leading ``name`` column (BED column 4, else ``<chrom> <first>-<last>``), then the
+usual columns in the usual order, ``window_start`` / ``window_end`` the region's 1-based inclusive bounds; one row
+per BED line in the file's order, a region without SNPs with ``snp_count`` 0 and empty fields.  ``--fst``,
+``--diversity`` and ``--null-*`` apply to it; ``--regions`` alone scans nothing else.
 """
 from __future__ import annotations
 
@@ -87,6 +94,30 @@ def write_csv(path, stats, chr_ids, fst=None, pixy=None, pvalues=False, diversit
             w.writerow(row)
 
 
+def write_regions_csv(path, rows, regions, chr_ids, fst=False, pvalues=False, diversity=False):
+    """``<prefix>_regions.csv``: write_csv's columns behind a leading ``name`` column, one row per region of
+    ``regions`` (a sfs2d.regions.Regions) in the caller's order; ``rows`` = the class's region rows."""
+    import twoDSFS_class as T
+    from .diversity import KEYS as D_COLS
+    cols = (["name"] + list(T.col_names) + (["FST"] if fst else []) + (D_COLS if diversity else [])
+            + (P_COLS if pvalues else []))
+    with open(path, "w", newline="") as fh:
+        w = csv.DictWriter(fh, fieldnames=cols)
+        w.writeheader()
+        for key, s in zip(regions.keys(), regions.slot.tolist()):
+            r = rows[key]
+            chrom = regions.chrom_names[int(regions.chrom[s])]
+            row = {"name": key, "chromosome": chr_ids.get(chrom, chrom), "window_start": int(regions.first[s]),
+                   "window_end": int(regions.last[s]), "snp_count": r["snp_count"], "T2D": r["T2D"],
+                   "T1D_p1": r["T1D_pop1"], "T1D_p2": r["T1D_pop2"], "new_term_p1": r["new_term_pop1"],
+                   "new_term_p2": r["new_term_pop2"], "T2D_diff": r.get("T2D_diff")}
+            if fst:
+                row["FST"] = r.get("FST")
+            for c in (D_COLS if diversity else []) + (P_COLS if pvalues else []):
+                row[c] = r.get(c)
+            w.writerow(row)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m sfs2d", description=__doc__.split("\n\n")[0])
     ap.add_argument("vcf")
@@ -114,11 +145,13 @@ def main(argv=None):
                          "single SNPs; needs --null-replicates")
     ap.add_argument("--diversity", action="store_true",
                     help="append per-window pi, dxy, da, Watterson's theta, S and Tajima's D (twelve columns)")
+    ap.add_argument("--regions", default=None, metavar="FILE.bed",
+                    help="scan the intervals of a BED file as windows of their own -> <prefix>_regions.csv")
     ap.add_argument("--out-prefix", default="stats")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="VCF parser threads (0 = all)")
     a = ap.parse_args(argv)
-    if not a.window and not a.snp_window:
+    if not a.window and not a.snp_window and a.regions is None:
         a.window = [20000]
     if a.null_replicates is not None and a.null_replicates < 1:
         ap.error("--null-replicates must be >= 1")
@@ -162,12 +195,25 @@ def main(argv=None):
                                          pop2_size=a.pop2_size, variant_type=a.variant_type, fold=not a.no_fold,
                                          device=a.device)
     outs = []
+    rg, rkw = None, {}
+    if a.regions is not None:   # (without the flag every call below is the one it was)
+        from .regions import Regions
+        rg = Regions.from_bed(packed, a.regions)
+        rkw = dict(regions=rg)
+
+    def regions_out(res):
+        if rg is None:
+            return
+        path = f"{a.out_prefix}_regions.csv"
+        write_regions_csv(path, res["regions"], rg, chr_ids, a.fst, null, a.diversity)
+        outs.append(path)
+        print(f"region_scan: {len(rg)} regions -> {path}", file=sys.stderr)
     t = time.perf_counter()
     if a.step is not None:   # sliding windows: every size from one upload and one k_prep pass
         if null:
-            res = obj.scan_pvalues(packed, a.window, step_size=a.step, fst=a.fst, **nkw, **dkw)
+            res = obj.scan_pvalues(packed, a.window, step_size=a.step, fst=a.fst, **nkw, **dkw, **rkw)
         else:
-            res = obj.multi_sliding_scan(packed, a.window, a.step, fst=a.fst, **dkw)
+            res = obj.multi_sliding_scan(packed, a.window, a.step, fst=a.fst, **dkw, **rkw)
         print(f"multi_sliding_scan ({len(a.window)} window sizes, step {a.step}): {time.perf_counter() - t:.2f} s",
               file=sys.stderr)
         for ws in a.window:
@@ -176,12 +222,13 @@ def main(argv=None):
             write_csv(path, rows, chr_ids, {k: r["FST"] for k, r in rows.items()} if a.fst else None, pixy, null, **dkw)
             outs.append(path)
             print(f"sliding_scan {ws} bp / {a.step} bp: {len(rows)} windows -> {path}", file=sys.stderr)
+        regions_out(res)
         return outs
     # every window size from one k_prep pass over the resident stream (sfs2d_plan_attach)
     if null:
-        res = obj.scan_pvalues(packed, a.window, a.snp_window, fst=a.fst, **nkw, **dkw)
+        res = obj.scan_pvalues(packed, a.window, a.snp_window, fst=a.fst, **nkw, **dkw, **rkw)
     else:
-        res = obj.multi_scan(packed, a.window, a.snp_window, fst=a.fst, **dkw)
+        res = obj.multi_scan(packed, a.window, a.snp_window, fst=a.fst, **dkw, **rkw)
     print(f"multi_scan ({len(a.window)} bp + {len(a.snp_window)} SNP-count window sizes): "
           f"{time.perf_counter() - t:.2f} s", file=sys.stderr)
     for ws in a.window:
@@ -196,6 +243,7 @@ def main(argv=None):
         write_csv(path, stats, chr_ids, fst, pixy, null, **dkw)
         outs.append(path)
         print(f"scan_perChr_bySNPs {S} SNPs: {len(stats)} windows -> {path}", file=sys.stderr)
+    regions_out(res)
     return outs
 
 

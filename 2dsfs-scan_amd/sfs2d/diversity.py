@@ -19,7 +19,8 @@ not.
 
 Per-site values divide the window's sums by its length in bp: the window size W for fixed-bp and sliding windows
 (every one of the W sites is taken as callable: a SNP-only VCF knows nothing else), ``pos[end-1] - pos[begin] + 1``
-for SNP-count windows.  S and Tajima's D are not scaled.
+for SNP-count windows, the region's own length ``last - first + 1`` for region windows.  S and Tajima's D are not
+scaled.
 """
 from __future__ import annotations
 
@@ -138,23 +139,33 @@ def _kind(mode):
     raise ValueError(f"mode must be 'bp' or 'snps' (or L.WINDOW_BP / L.WINDOW_SNPS), got {mode!r}")
 
 
-def rows(recs, div, packed, window, mode, step=None, pop_sizes=None) -> dict:
+def rows(recs, div, packed, window, mode, step=None, pop_sizes=None, regions=None) -> dict:
     """{window label: the twelve KEYS} from a plan's window records ``recs`` and its diversity records ``div``
     (same index), labels as the scans make them (post.record_labels: ``mode`` "bp" with ``window`` bp, sliding by
     ``step``; or "snps" with ``window`` SNPs per window).  Records that are no window (empty slots, the Q9 helper, an
     S-SNP window without 2D SFS entries) give no row.  pi, dxy, da = dxy - (pi1 + pi2) / 2 and theta_W are per
     site (module docstring); S, S_full and Tajima's D are not scaled.  ``pop_sizes`` = (pop1_size, pop2_size)
     diploid individuals: Tajima's D is formed from the SNPs fully called in the population (n = 2 pop_size); without
-    it the two tajima_d columns are None."""
-    kind = _kind(mode)
+    it the two tajima_d columns are None.  ``regions`` (the Regions of a regions plan; ``window`` / ``mode`` /
+    ``step`` unused): the keys are the regions' row keys, the per-site divisor each region's own length
+    ``last - first + 1``, and an empty region has a row of twelve None (post.region_scan gives it a row too)."""
     if len(recs) != len(div):
         raise ValueError("window records and diversity records differ in length")
-    labels = post.record_labels(recs, packed, kind, int(window), step)
+    spans = None
+    if regions is not None:
+        kind = "regions"
+        labels = post.region_labels(recs, regions)
+        spans = regions.lengths()
+    else:
+        kind = _kind(mode)
+        labels = post.record_labels(recs, packed, kind, int(window), step)
     out = {}
-    for r, d, lb in zip(recs, div, labels):
+    for i, (r, d, lb) in enumerate(zip(recs, div, labels)):
         if lb is None:
             continue
-        if kind == "bp":
+        if spans is not None:
+            span = float(int(spans[i]))
+        elif kind == "bp":
             span = float(int(window))
         else:
             span = float(int(packed.pos[int(r["end"]) - 1]) - int(packed.pos[int(r["begin"])]) + 1)
@@ -168,12 +179,16 @@ def rows(recs, div, packed, window, mode, step=None, pop_sizes=None) -> dict:
             row["tajima_d_pop1"] = tajima_d(2 * int(pop_sizes[0]), d["s1_full"], d["ar1_full"])
             row["tajima_d_pop2"] = tajima_d(2 * int(pop_sizes[1]), d["s2_full"], d["ar2_full"])
         out[lb] = row
+    if regions is not None:
+        for r, k in zip(recs, regions.slot_keys()):
+            if r["flags"] & L.W_EMPTY:
+                out[k] = dict.fromkeys(KEYS)
     return out
 
 
-def add_columns(stats, recs, div, packed, window, mode, step=None, pop_sizes=None):
+def add_columns(stats, recs, div, packed, window, mode, step=None, pop_sizes=None, regions=None):
     """Add the twelve KEYS to every row of a scan's result dict ``stats`` (the rows of ``recs``' windows)."""
-    dv = rows(recs, div, packed, window, mode, step, pop_sizes)
+    dv = rows(recs, div, packed, window, mode, step, pop_sizes, regions)
     for lb, row in stats.items():
         row.update(dv[lb])
     return stats

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib as L
 from .pack import PackedSNPs
+from .regions import Regions
 
 
 @dataclass
@@ -30,8 +31,15 @@ class ScanConfig:
     prev_extra: bool = False
     fst: bool = False          # also compute Hudson's Fst per window slot (Plan.read_fst)
     scan_wgs_per_cu: int = 0   # cap on scan workgroups per CU (0: all that fit; see sfs2d_params)
+    regions: Optional[Regions] = None   # region windows: the plan's windows are these intervals (sfs2d.regions;
+                                        # fixed-bp mode, `window` is not geometry); exclusive with `step`; passed to
+                                        # the regions entry points as `step` is to the sliding ones (not part of params())
     step: Optional[int] = None   # sliding windows: fixed-bp windows advanced by `step` bp (None: disjoint windows);
                                  # not part of params(): Engine.plan / Plan.attach pass it to the sliding entry points
+
+    def __post_init__(self):
+        if self.regions is not None and self.step is not None:
+            raise ValueError("ScanConfig: regions and step are exclusive (regions are not placed by a rule)")
 
     def params(self) -> L.Params:
         p = L.Params()
@@ -196,7 +204,16 @@ class Plan:
         self.h = C.c_void_p()
         self.attached = []
         prm = cfg.params()
-        if base is None and cfg.step is None:
+        rg = cfg.regions
+        if rg is not None and cfg.step is not None:
+            raise ValueError("ScanConfig: regions and step are exclusive (regions are not placed by a rule)")
+        if rg is not None and base is None:
+            eng.check(eng.lib.sfs2d_plan_create_regions(eng.h, data.h, C.byref(prm), L.ptr(rg.chrom), L.ptr(rg.first),
+                                                        L.ptr(rg.last), len(rg), C.byref(self.h)))
+        elif rg is not None:
+            eng.check(eng.lib.sfs2d_plan_attach_regions(base.h, C.byref(prm), L.ptr(rg.chrom), L.ptr(rg.first),
+                                                        L.ptr(rg.last), len(rg), C.byref(self.h)))
+        elif base is None and cfg.step is None:
             eng.check(eng.lib.sfs2d_plan_create(eng.h, data.h, C.byref(prm), C.byref(self.h)))
         elif base is None:
             eng.check(eng.lib.sfs2d_plan_create_sliding(eng.h, data.h, C.byref(prm), int(cfg.step), C.byref(self.h)))
@@ -210,8 +227,8 @@ class Plan:
 
     def attach(self, cfg: ScanConfig) -> "Plan":
         """A plan scanned from this plan's k_prep pass (another window size / SNP-count windows, or with
-        ``cfg.step`` sliding windows): run this (base) plan, then read the attached one
-        (sfs2d_plan_attach / sfs2d_plan_attach_sliding)."""
+        ``cfg.step`` sliding windows, or with ``cfg.regions`` a list of intervals): run this (base) plan, then read
+        the attached one (sfs2d_plan_attach / sfs2d_plan_attach_sliding / sfs2d_plan_attach_regions)."""
         return Plan(self.eng, self.data, cfg, base=self)
 
     def set_background(self, bg2d, bg1a, bg1b):
@@ -371,7 +388,7 @@ class Plan:
 
     def seg_kind(self) -> str:
         """Where this plan's window slots come from (sfs2d_plan_seg_kind): "prep", "index", "search", "synth",
-        "slide", "bp" or "none"."""
+        "slide", "regions", "bp" or "none"."""
         return self.eng.lib.sfs2d_plan_seg_kind(self.h).decode()
 
     def slots_once(self) -> bool:

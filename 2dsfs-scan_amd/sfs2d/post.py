@@ -151,6 +151,43 @@ def sliding_scan(recs, packed, ws, step, fst=None):
     return res
 
 
+def region_scan(recs, packed, regions, fst=None):
+    """Rows of a regions plan (sfs2d_plan_create_regions; ``regions``: the sfs2d.regions.Regions the plan was made
+    from, record s = its slot s): {key: row} with ONE ROW PER REGION in the caller's order, the key the region's
+    name or "<chrom> <first>-<last>".  A row holds the seven keys of combined_scan, plus "FST" (None for NaN) when
+    ``fst`` (the plan's Fst per slot) is given, with sliding_scan's clean None rules.  An empty region is a row too
+    -- a gene without SNPs is an answer: snp_count 0 and every statistic None."""
+    if len(recs) != len(regions):
+        raise ValueError(f"{len(recs)} records for {len(regions)} regions")
+    res = {}
+    for key, s in zip(regions.keys(), regions.slot.tolist()):
+        if key in res:
+            raise ValueError(f"duplicate region key {key!r}")
+        r = recs[s]
+        if r["flags"] & L.W_EMPTY:
+            row = {"snp_count": 0, "T2D": None, "T1D_pop1": None, "T1D_pop2": None, "new_term_pop1": None,
+                   "new_term_pop2": None, "T2D_diff": None}
+            if fst is not None:
+                row["FST"] = None
+        else:
+            T2D, T1, T2 = _v(r, 2), _v(r, 1), _v(r, 0)
+            row = {"snp_count": int(r["snp_count"]), "T2D": T2D, "T1D_pop1": T1, "T1D_pop2": T2,
+                   "new_term_pop1": None if T2D is None or T1 is None else T2D - T1,
+                   "new_term_pop2": None if T2D is None or T2 is None else T2D - T2,
+                   "T2D_diff": None if T2D is None or T1 is None or T2 is None else T2D - (T1 + T2) / 2}
+            if fst is not None:
+                row["FST"] = None if np.isnan(fst[s]) else float(fst[s])
+        res[key] = row
+    return res
+
+
+def region_labels(recs, regions):
+    """The row key of every record of a regions plan, in slot order (None: an empty region -- it has a row, with
+    no statistic to put beside; record_labels' convention)."""
+    keys = regions.slot_keys()
+    return [None if r["flags"] & L.W_EMPTY else k for r, k in zip(recs, keys)]
+
+
 def single_stat_scan(recs, packed, ws, nslots, which, name):
     """T1D_scan (539-623) / T2D_scan (686-776): {label: {"snp_count", name}} per non-empty fixed-bp
     window, the statistic None for an empty window or background (no guard, no derived terms).

@@ -270,7 +270,7 @@ class LikelihoodInference_jointSFS:
         return post.single_stat_scan(recs, q, window_size, post.num_slots(recs), 2, "T2D")
 
     # ------------------------------------------------------------------ multi-resolution (extension)
-    def multi_scan(self, data_dict, window_sizes=(), snp_window_sizes=(), fst=False, diversity=False):
+    def multi_scan(self, data_dict, window_sizes=(), snp_window_sizes=(), fst=False, diversity=False, regions=None):
         """combined_scan at every size in ``window_sizes`` and scan_perChr_bySNPs at every size in
         ``snp_window_sizes`` from ONE pass over the SNP stream (the reference script runs these
         scans one after another over the same data, twoDSFS_class.py:1923-2032): the smallest
@@ -278,8 +278,12 @@ class LikelihoodInference_jointSFS:
         Returns {ws: combined_scan result, "<S>snps": scan_perChr_bySNPs result}, plus
         {"fst": {ws: window_fst result}} when ``fst`` (fixed-bp windows only).  ``diversity``: every row
         also holds the twelve columns of ``window_diversity`` (sfs2d.diversity.KEYS), summed on the GPU over
-        the same resident data (k_div_win after the run)."""
-        return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, diversity=diversity)
+        the same resident data (k_div_win after the run).  ``regions`` (as in ``region_scan``): the per-region rows
+        as well, under the "regions" key, from a regions plan attached to the same base -- the tiled scan and the
+        per-gene rows from one pass."""
+        if regions is None:
+            return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, diversity=diversity)
+        return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, diversity=diversity, regions=regions)
 
     def _no_distributed_diversity(self, diversity):
         if diversity and self.distributed:
@@ -288,21 +292,94 @@ class LikelihoodInference_jointSFS:
     def _add_diversity(self, rows, recs, pl, p, kind, w, step=None):
         """The twelve diversity columns into ``rows`` (the result rows of plan ``pl``'s records ``recs``)."""
         from sfs2d import diversity as DV
-        DV.add_columns(rows, recs, pl.diversity(), p, w, kind, step, (self.pop1_size, self.pop2_size))
+        DV.add_columns(rows, recs, pl.diversity(), p, w, kind, step, (self.pop1_size, self.pop2_size),
+                       **({"regions": pl.cfg.regions} if kind == "regions" else {}))
 
-    def _multi_scan(self, data_dict, window_sizes, snp_window_sizes, fst, after_run=None, diversity=False):
+    # ------------------------------------------------------------------ region windows (extension)
+    def _no_distributed_regions(self, what):
+        if self.distributed:
+            raise NotImplementedError(f"{what} is single-GPU (distributed sharding of regions is not implemented)")
+
+    @staticmethod
+    def _regions_of(p, regions):
+        """``regions`` (a sfs2d.regions.Regions, a BED path, or (chrom_name, first, last[, name]) tuples) as a
+        Regions against ``p``'s chromosome names; ValueError for an unknown chromosome, first > last, a duplicate
+        row key -- before any GPU work."""
+        from sfs2d.regions import Regions
+        return Regions.of(p, regions)
+
+    def _region_rows(self, p, pl, rg, recs, fst, diversity):
+        """The rows of regions plan ``pl`` (run, alive) from its records."""
+        rows = post.region_scan(recs, p, rg, pl.read_fst() if fst else None)
+        if diversity:
+            self._add_diversity(rows, recs, pl, p, "regions", None)
+        return rows
+
+    @staticmethod
+    def _null_fill(rows):
+        """p_* keys of the rows the null left out (empty regions): None."""
+        from sfs2d import null as N
+        for row in rows.values():
+            for key in N.P_KEYS:
+                row.setdefault(key, None)
+
+    def region_scan(self, data_dict, regions, background_chromosome=None, fst=False, diversity=False):
+        """The intervals of ``regions`` -- annotated genes, a known inversion, candidate regions, a QTL interval --
+        scanned as windows (sfs2d_plan_create_regions).  ``regions``: a
+        sfs2d.regions.Regions, a BED file path, or ``(chrom_name, first, last[, name])`` tuples with 1-based
+        inclusive positions; they may overlap, nest, repeat and come in any order.  The reference has no such
+        scan: its users tile the genome and cut the tiles that overlap each gene out of the table afterwards.
+        ``background_chromosome`` None: each chromosome is its own background, the whole chromosome whether or
+        not regions cover it (as combined_scan); else that chromosome's SFS for every region (as scan_chooseChr).
+        Returns {key: row}, one row PER REGION in the caller's order, the key the region's name or
+        "<chrom> <first>-<last>": combined_scan's seven keys, plus "FST" when ``fst`` and the twelve diversity
+        columns (per site of the region's own length) when ``diversity``; clean None rules (post.region_scan); a
+        region without SNPs has snp_count 0 and None everywhere."""
+        self._no_distributed_diversity(diversity)
+        self._no_distributed_regions("region_scan")
+        p = self._pack(data_dict)
+        rg = self._regions_of(p, regions)
+        bg = None
+        if background_chromosome is not None:
+            if background_chromosome not in p.chrom_names:
+                raise ValueError(f"Background chromosome {background_chromosome} not found in the data.")
+            bg = self._bg_arrays(p, p.chrom_names.index(background_chromosome))
+        cfg = self._cfg(p, window_mode=L.WINDOW_BP, fst=bool(fst), regions=rg,
+                        bg_mode=L.BG_PER_CHROM if bg is None else L.BG_SUPPLIED)
+        eng = self._engine()
+        dev = eng.upload(p)
+        try:
+            pl = eng.plan(dev, cfg)
+            try:
+                if bg is not None:
+                    pl.set_background(*bg)
+                pl.run()
+                pl.check()
+                rows = self._region_rows(p, pl, rg, pl.read(), fst, diversity)
+            finally:
+                pl.close()
+        finally:
+            dev.close()
+        return rows
+
+    def _multi_scan(self, data_dict, window_sizes, snp_window_sizes, fst, after_run=None, diversity=False, regions=None):
         """multi_scan; ``after_run(p, base plan, [(recs, record labels, rows)])`` is called while the
         plans are alive (scan_pvalues adds its columns there)."""
         self._no_distributed_diversity(diversity)
+        if regions is not None:
+            self._no_distributed_regions("multi_scan with regions")
         p = self._pack(data_dict)
+        rg = None if regions is None else self._regions_of(p, regions)
         bps = sorted(set(int(w) for w in window_sizes))
         snps = [int(x) for x in dict.fromkeys(snp_window_sizes)]
-        if not bps and not snps:
+        if not bps and not snps and rg is None:
             return {}
-        specs = [("bp", w) for w in bps] + [("snps", S) for S in snps]
+        specs = [("bp", w) for w in bps] + [("snps", S) for S in snps] + ([("regions", None)] if rg is not None else [])
         base_ws = bps[0] if bps else None
 
         def cfg_of(kind, w):
+            if kind == "regions":   # (its Fst needs nothing of the base)
+                return self._cfg(p, window_mode=L.WINDOW_BP, bg_mode=L.BG_PER_CHROM, fst=bool(fst), regions=rg)
             bp = kind == "bp"
             want_fst = fst and bp and base_ws is not None   # (the library refuses what it cannot attach)
             return self._cfg(p, window_mode=L.WINDOW_BP if bp else L.WINDOW_SNPS, window=w,
@@ -329,6 +406,11 @@ class LikelihoodInference_jointSFS:
                 for (kind, w), pl in zip(specs, plans):
                     pl.check()
                     recs = pl.read()
+                    if kind == "regions":
+                        out["regions"] = self._region_rows(p, pl, rg, recs, fst, diversity)
+                        if after_run is not None:
+                            items.append((recs, post.region_labels(recs, rg), out["regions"]))
+                        continue
                     if kind == "bp":
                         out[w] = post.combined_scan(recs, p, w, post.num_slots(recs))
                         if pl.cfg.fst:
@@ -341,6 +423,8 @@ class LikelihoodInference_jointSFS:
                         items.append((recs, post.record_labels(recs, p, kind, w), out[w if kind == "bp" else f"{w}snps"]))
                 if after_run is not None:
                     after_run(p, base, items)
+                    if rg is not None:
+                        self._null_fill(out["regions"])
             finally:
                 base.close()
         finally:
@@ -407,23 +491,27 @@ class LikelihoodInference_jointSFS:
             dev.close()
         return rows
 
-    def multi_sliding_scan(self, data_dict, window_sizes, step_size, fst=False, diversity=False):
+    def multi_sliding_scan(self, data_dict, window_sizes, step_size, fst=False, diversity=False, regions=None):
         """sliding_scan (per-chromosome backgrounds) at every size in ``window_sizes`` with one step, from
         ONE upload and one k_prep pass: the smallest window is a sliding plan of its own, the others are
         attached to it (sfs2d_plan_attach_sliding).  Returns {window_size: sliding_scan rows}.  A window the
-        step does not divide raises ValueError before any GPU work.  ``diversity``: as in multi_scan."""
-        return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, diversity=diversity)
+        step does not divide raises ValueError before any GPU work.  ``diversity``, ``regions``: as in multi_scan."""
+        if regions is None:
+            return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, diversity=diversity)
+        return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, diversity=diversity, regions=regions)
 
-    def _multi_sliding_scan(self, data_dict, window_sizes, step_size, fst, after_run=None, diversity=False):
+    def _multi_sliding_scan(self, data_dict, window_sizes, step_size, fst, after_run=None, diversity=False, regions=None):
         """multi_sliding_scan, with ``after_run`` as in _multi_scan."""
         self._no_distributed_diversity(diversity)
         if self.distributed:
             raise NotImplementedError("multi_sliding_scan is single-GPU (distributed sharding of sliding windows is not implemented)")
         wss = sorted(set(int(w) for w in window_sizes))
         step = self._check_steps(wss, step_size)
-        if not wss:
+        if not wss and regions is None:
             return {}
         p = self._pack(data_dict)
+        rg = None if regions is None else self._regions_of(p, regions)
+        rcfg = None if rg is None else self._cfg(p, window_mode=L.WINDOW_BP, bg_mode=L.BG_PER_CHROM, fst=bool(fst), regions=rg)
 
         def cfg_of(w):
             return self._cfg(p, window_mode=L.WINDOW_BP, window=w, bg_mode=L.BG_PER_CHROM, fst=bool(fst), step=step)
@@ -431,9 +519,10 @@ class LikelihoodInference_jointSFS:
         dev = eng.upload(p)
         out = {}
         try:
-            base = eng.plan(dev, cfg_of(wss[0]))
+            base = eng.plan(dev, cfg_of(wss[0]) if wss else rcfg)
             try:
                 plans = [base] + [base.attach(cfg_of(w)) for w in wss[1:]]
+                rpl = None if rg is None else base.attach(rcfg) if wss else base
                 base.run()
                 base.check()
                 items = []
@@ -445,8 +534,16 @@ class LikelihoodInference_jointSFS:
                         self._add_diversity(out[w], recs, pl, p, "bp", w, step)
                     if after_run is not None:
                         items.append((recs, post.record_labels(recs, p, "bp", w, step), out[w]))
+                if rpl is not None:
+                    rpl.check()
+                    recs = rpl.read()
+                    out["regions"] = self._region_rows(p, rpl, rg, recs, fst, diversity)
+                    if after_run is not None:
+                        items.append((recs, post.region_labels(recs, rg), out["regions"]))
                 if after_run is not None:
                     after_run(p, base, items)
+                    if rg is not None:
+                        self._null_fill(out["regions"])
             finally:
                 base.close()
         finally:
@@ -508,7 +605,7 @@ class LikelihoodInference_jointSFS:
 
     def scan_pvalues(self, data_dict, window_sizes=(), snp_window_sizes=(), step_size=None,
                      background_chromosome=None, replicates=999, seed=0, sizes=None, fst=False, block=None,
-                     diversity=False):
+                     diversity=False, regions=None):
         """The scans of ``multi_scan`` (``step_size`` given: ``multi_sliding_scan``) with a bootstrap p-value
         beside every statistic: each row additionally holds p_T2D, p_T1D_pop1, p_T1D_pop2, p_new_term_pop1,
         p_new_term_pop2 and p_T2D_diff -- the share of ``replicates`` windows of the same number of SNPs
@@ -524,7 +621,11 @@ class LikelihoodInference_jointSFS:
         ``background_chromosome``: one window size, scanned as scan_chooseChr (or scan_chooseChr_bySNPs for a
         SNP-count size, sliding_scan with ``step_size``) does; that chromosome is every window's pool; the
         result is {size: rows}.  ``diversity``: every row also holds the twelve diversity columns
-        (``window_diversity``; they get no p-values).  Not in the reference (it thresholds by SNP-count quantile and top 1 % in R,
+        (``window_diversity``; they get no p-values).  ``regions`` (as in ``region_scan``): the per-region rows as
+        well, under the "regions" key, from a regions plan attached to the same base; a region's pool is its
+        chromosome (or ``background_chromosome``, then without window sizes: {"regions": rows}), its m its SNP
+        count end - begin through the same size classes, blocks and p-value rule; an empty region's p-values are
+        None.  Not in the reference (it thresholds by SNP-count quantile and top 1 % in R,
         ECBstats_plots.R:45-50, 147-219)."""
         self._no_distributed_diversity(diversity)
         if self.distributed:
@@ -534,17 +635,21 @@ class LikelihoodInference_jointSFS:
         if sizes is not None and sizes != "exact":
             sizes = sorted(int(x) for x in sizes)
         block = self._null_block(block)
+        rkw = {} if regions is None else {"regions": regions}
 
         def hook(pool=None):
             return lambda p, base, items: self._null_columns(p, base, items, replicates, seed, sizes, pool, block)
         if background_chromosome is None:
             if step_size is None:
-                return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, hook(), diversity=diversity)
+                return self._multi_scan(data_dict, window_sizes, snp_window_sizes, fst, hook(), diversity=diversity, **rkw)
             if len(tuple(snp_window_sizes)):
                 raise ValueError("step_size applies to fixed-bp windows: not with snp_window_sizes")
-            return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, hook(), diversity=diversity)
+            return self._multi_sliding_scan(data_dict, window_sizes, step_size, fst, hook(), diversity=diversity, **rkw)
         # one chromosome as every window's background (and pool)
         bps, snps = [int(w) for w in window_sizes], [int(w) for w in snp_window_sizes]
+        if regions is not None:
+            return self._region_pvalues(data_dict, regions, bps, snps, step_size, background_chromosome, replicates,
+                                        seed, sizes, fst, block, diversity)
         if len(bps) + len(snps) != 1:
             raise ValueError("background_chromosome takes exactly one window size")
         if step_size is not None and snps:
@@ -586,6 +691,37 @@ class LikelihoodInference_jointSFS:
         finally:
             dev.close()
         return {(f"{w}snps" if snps else w): rows}
+
+    def _region_pvalues(self, data_dict, regions, bps, snps, step_size, background_chromosome, replicates, seed,
+                        sizes, fst, block, diversity):
+        """scan_pvalues with ``regions`` and one chromosome as every region's background and pool."""
+        if bps or snps or step_size is not None:
+            raise ValueError("regions with background_chromosome take no window sizes and no step_size")
+        p = self._pack(data_dict)
+        rg = self._regions_of(p, regions)
+        if background_chromosome not in p.chrom_names:
+            raise ValueError(f"Background chromosome {background_chromosome} not found in the data.")
+        bgc = p.chrom_names.index(background_chromosome)
+        bg = self._bg_arrays(p, bgc)
+        cfg = self._cfg(p, window_mode=L.WINDOW_BP, bg_mode=L.BG_SUPPLIED, fst=bool(fst), regions=rg)
+        eng = self._engine()
+        dev = eng.upload(p)
+        try:
+            pl = eng.plan(dev, cfg)
+            try:
+                pl.set_background(*bg)
+                pl.run()
+                pl.check()
+                recs = pl.read()
+                rows = self._region_rows(p, pl, rg, recs, fst, diversity)
+                self._null_columns(p, pl, [(recs, post.region_labels(recs, rg), rows)], replicates, seed, sizes,
+                                   pool=bgc, block=block)
+                self._null_fill(rows)
+            finally:
+                pl.close()
+        finally:
+            dev.close()
+        return {"regions": rows}
 
     # ------------------------------------------------------------------ Fst (extension)
     def window_fst(self, data_dict, window_size=None, snp_window_size=None):

@@ -39,7 +39,8 @@ extern "C" {
  * sfs2d_graph_* added (round 6, additive); sfs2d_plan_create_sliding / sfs2d_plan_attach_sliding added
  * (additive: sfs2d_params keeps its layout, the step is an argument); sfs2d_plan_null_run / _null_read added
  * (additive); sfs2d_plan_null_run_blocks added (additive: sfs2d_null_params keeps its layout, the block length is
- * an argument); sfs2d_plan_diversity / _diversity_read and sfs2d_diversity added (additive) */
+ * an argument); sfs2d_plan_diversity / _diversity_read and sfs2d_diversity added (additive);
+ * sfs2d_plan_create_regions / sfs2d_plan_attach_regions added (additive: the intervals are arguments) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -273,6 +274,35 @@ int sfs2d_plan_create_sliding(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2
  * 500 kb pair of twoDSFS_class.py:1923-1932 as two sliding scans of one read of the SNP stream.  Fst of
  * an attached sliding plan needs nothing of the base (no Fst flag, no dividing window). */
 int sfs2d_plan_attach_sliding(sfs2d_plan* base, const sfs2d_params* params, int64_t step, sfs2d_plan** out);
+/* Region windows: a fixed-bp plan (params->window_mode == SFS2D_WINDOW_BP) whose windows
+ * are the caller's n intervals instead of tiles placed by a rule -- genes, an inversion, candidate regions.
+ * Region i is (chrom[i], first[i], last[i]): chrom an index into the data set's chromosomes, first <= last
+ * 1-based inclusive positions below 2^32.  It holds the SNPs of that chromosome with first <= pos <= last:
+ * begin = the chromosome's first SNP with pos >= first, end = the first with pos >= last + 1 (in 64 bits:
+ * last = 2^32 - 1 is legal); repeated positions at a boundary are all inside; a SNP at pos 0 is inside only
+ * when first == 0.  Regions may overlap, nest, repeat and come in any order within a chromosome, but chrom must
+ * be non-decreasing over the list (a chromosome's slots are contiguous); a chromosome may have no region, and a
+ * region may lie on a chromosome without SNPs.  Region i is slot i and record i: chrom its chromosome, wid its
+ * index within the chromosome's regions, begin / end as above, an empty range an SFS2D_W_EMPTY record.  The three
+ * arrays are HOST arrays, copied to the device once; n >= 1 and n < 2^31.  params->window is not geometry here
+ * (any legal value): the plan's copy holds the longest region's length last - first + 1 (2^32 - 1 for the one
+ * length above it).  Filters keep their meaning (SFS membership, not geometry); a per-chromosome background is
+ * the whole chromosome, counted once, whether or not regions cover it.  Everything else is a sliding plan's:
+ * sfs2d_plan_run, _run_many, _run_streams, _read, _fst_read (every regions plan with SFS2D_F_FST produces Fst),
+ * _check, timing, sfs2d_graph_*, sfs2d_plan_diversity, sfs2d_plan_null_run(_blocks); sfs2d_plan_seg_kind says
+ * "regions".  The 2D bins in LDS are 16-bit when no region holds 65,536 SNPs or more, counted exactly from the
+ * library's host copy of the positions (sfs2d_data_upload); wrapped device arrays always take 32-bit bins.
+ * SFS2D_E_ARG, the reason in sfs2d_last_error: a null array, n < 1, n >= 2^31, chrom out of range or decreasing,
+ * first > last, SFS2D_F_PREV_EXTRA, SNP-count windows.
+ * The reference has no such scan, nor anything in its place: it writes tiled windows (twoDSFS_class.py:787-991)
+ * and its users cut the intervals they care about out of those tables afterwards. */
+int sfs2d_plan_create_regions(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_params* params, const int32_t* chrom,
+                              const uint32_t* first, const uint32_t* last, int64_t n, sfs2d_plan** out);
+/* The same as an attached plan (the rules of sfs2d_plan_attach_sliding; `base` is an ordinary, a sliding or a
+ * regions plan): the tiled scan and the per-region records from ONE k_prep pass of the base.  Its Fst needs
+ * nothing of the base.  An ordinary plan attached to a regions base is treated as one attached to a sliding base. */
+int sfs2d_plan_attach_regions(sfs2d_plan* base, const sfs2d_params* params, const int32_t* chrom,
+                              const uint32_t* first, const uint32_t* last, int64_t n, sfs2d_plan** out);
 /* Bootstrap null of T2D / T1D: how large is a window's T under "this window is a random
  * sample of its background"?  A task is a pair (pool, m): pool = a chromosome index c, meaning the SNPs
  * [chrom_off[c], chrom_off[c+1]) of the plan's data set, or -1, all of them (every SNP of the range, whatever
@@ -351,7 +381,7 @@ const char* sfs2d_plan_scan_kernel(const sfs2d_plan* plan);
  * (k_slots_index over the data set's position index, ahead of a k_prep that reads no positions: fixed-bp
  * counts plans with per-chromosome backgrounds over uploaded or generated data, unless SFS2D_SEG=prep at plan
  * creation), "search"
- * (k_slots_search), "synth" (the generator's window offsets), "slide" (k_slots_slide), "bp" (an attached
+ * (k_slots_search), "synth" (the generator's window offsets), "slide" (k_slots_slide), "regions" (k_slots_regions), "bp" (an attached
  * fixed-bp plan: k_slots_bp), "none" (SNP-count windows); NULL for a null plan */
 const char* sfs2d_plan_seg_kind(const sfs2d_plan* plan);
 /* 1: the plan's slot table is written by its first run alone and later runs launch no slot kernel -- "index"
