@@ -12,6 +12,8 @@
 // Fst itself, and the same scan kernels.
 // After a run, sfs2d_plan_diversity enqueues k_div_win (sfs2d_div.hpp) over the run's records: per-window pi, dxy,
 // Watterson and Tajima sums from the resident counts; it writes its own output alone.
+// sfs2d_plan_spectra enqueues k_spec_win (sfs2d_spec.hpp) over chosen records of the run: their 2D and folded 1D
+// spectra themselves, summed into groups, as int64 rows; it too writes its own output alone.
 // All device state a run touches (slot table, background replicas and counters, LDS) is left
 // zeroed by the run itself, so plans replay without memsets.
 #include <hip/hip_runtime.h>
@@ -32,6 +34,7 @@
 #include "sfs2d.h"
 #include "sfs2d_kernels.hpp"
 #include "sfs2d_div.hpp"
+#include "sfs2d_spec.hpp"
 
 using namespace sfs2dk;
 
@@ -253,6 +256,15 @@ struct sfs2d_plan {
   sfs2d_diversity* d_div = nullptr;
   const sfs2d_diversity* div_last = nullptr;
   int64_t div_nrec = -1;                 // records of the last call (-1: none yet)
+  // window spectra (sfs2d_plan_spectra): the last call's selection, the plan-owned rows and where the call wrote
+  std::vector<SpecSel> spec_sel_h;
+  SpecSel* d_spec_sel = nullptr;
+  size_t spec_sel_cap = 0;
+  int64_t* d_spec = nullptr;             // plan-owned rows (out_dev == NULL)
+  size_t spec_cap = 0;                   // ... in int64 words
+  const int64_t* spec_last = nullptr;
+  int64_t spec_words = -1;               // words of the last call (-1: none yet)
+  int spec_lds_ok = -1;                  // the row's LDS histogram: -1 not asked yet, 1 granted, 0 refused (global atomics)
   uint64_t null_tab_runs = ~0ull;        // fused / sliced plans: the run whose tables of EVERY chromosome are in
                                          // d_tab / d_lp / d_head (their scans keep all but one chromosome's in LDS)
 };
@@ -300,6 +312,7 @@ void plan_free(sfs2d_plan* p) {
   hipFree(p->d_bg1d); hipFree(p->d_leafsum); hipFree(p->d_leaves); hipFree(p->d_nodes); hipFree(p->d_slices);
   hipFree(p->d_out); hipFree(p->d_err); hipFree(p->d_bins); hipFree(p->d_fst_own); hipFree(p->d_fsum); hipFree(p->d_gscr);
   hipFree(p->d_ntask); hipFree(p->d_null); hipFree(p->d_div);
+  hipFree(p->d_spec_sel); hipFree(p->d_spec);
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->tev) if (e) hipEventDestroy(e);
 }
@@ -388,6 +401,16 @@ struct Prep {   // k_prep<DO_BG, DO_SEG, LDS_HIST, DO_BINS, FILT, FST, JNT>
     return bg || seg || bins || fst;   // (a pass with nothing to do is not launched: prep_runs)
   }
   template <int I> static constexpr Fn kernel() { constexpr Prep s = at(I); return k_prep<s.bg, s.seg, s.lds, s.bins, s.filt, s.fst, s.jnt>; }
+};
+
+struct SpecWin {   // k_spec_win<CNT, LDSH>
+  bool cnt, ldsh;
+  using Fn = decltype(&k_spec_win<true, true>);
+  static constexpr int N = 4;
+  constexpr int index() const { return cnt | ldsh << 1; }
+  static constexpr SpecWin at(int i) { return {bool(i & 1), bool(i & 2)}; }
+  constexpr bool legal() const { return true; }
+  template <int I> static constexpr Fn kernel() { constexpr SpecWin s = at(I); return k_spec_win<s.cnt, s.ldsh>; }
 };
 
 // entry I of family S's table: its kernel, instantiated only where the selection is legal
@@ -2337,6 +2360,119 @@ int sfs2d_plan_diversity_read(sfs2d_plan* pl, sfs2d_diversity* out_host, int64_t
   if (pl->div_nrec && !out_host) return SFS2D_E_ARG;
   if (pl->div_nrec)
     HIPCHK(ctx, hipMemcpyAsync(out_host, pl->div_last, sizeof(sfs2d_diversity) * (size_t)pl->div_nrec, hipMemcpyDeviceToHost,
+                               CTX_STREAM(ctx)));
+  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------ window spectra
+
+int sfs2d_plan_spectra(sfs2d_plan* pl, const int64_t* rec, const int32_t* grp, int64_t nsel, int64_t ngroups,
+                       int64_t* out_dev) {
+  if (!pl) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  const sfs2d_data* d = pl->data;
+  if (pl->runs == 0)
+    return set_err(ctx, SFS2D_E_ARG, pl->base ? "spectra before the base plan's first run (an attached plan has no records yet)"
+                                              : "spectra before the plan's first run (no records yet)");
+  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "spectra: data set too large for 32-bit SNP indices");
+  if (nsel < 0) return set_err(ctx, SFS2D_E_ARG, "spectra: nsel must be >= 0");
+  if (ngroups < 1) return set_err(ctx, SFS2D_E_ARG, "spectra: ngroups must be >= 1");
+  if (!rec && nsel != pl->nrec)
+    return set_err(ctx, SFS2D_E_ARG, "spectra: rec == NULL selects every record in order: nsel must be the plan's record count");
+  if (rec && !grp) return set_err(ctx, SFS2D_E_ARG, "spectra: grp == NULL needs rec == NULL (group i = record i)");
+  if (nsel > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "spectra: more than 2^32 - 1 selection entries");
+  if (!grp && nsel > ngroups)
+    return set_err(ctx, SFS2D_E_ARG, "spectra: group i = record i needs ngroups >= the plan's record count");
+  pl->spec_sel_h.resize((size_t)nsel);
+  int64_t nruns = 0, prev_g = -1;   // maximal runs of consecutive entries of one group
+  for (int64_t i = 0; i < nsel; ++i) {
+    const int64_t r = rec ? rec[i] : i, g = grp ? (int64_t)grp[i] : i;
+    if (r < 0 || r >= pl->nrec)
+      return set_err(ctx, SFS2D_E_ARG, "spectra: entry " + std::to_string(i) + ": record " + std::to_string(r) +
+                                           " outside [0, " + std::to_string(pl->nrec) + ")");
+    if (g < 0 || g >= ngroups)
+      return set_err(ctx, SFS2D_E_ARG, "spectra: entry " + std::to_string(i) + ": group " + std::to_string(g) +
+                                           " outside [0, " + std::to_string(ngroups) + ")");
+    pl->spec_sel_h[(size_t)i] = SpecSel{(uint32_t)r, (uint32_t)g};
+    nruns += g != prev_g;
+    prev_g = g;
+  }
+  // groups x row in 64 bits: the row is at most 255 x 255 + 256 words
+  const int64_t roww = (int64_t)pl->K.nb2 + pl->K.n1p + pl->K.n2p + 2;
+  if (ngroups > 0xffffffffll || ngroups > (INT64_MAX / 8) / roww)
+    return set_err(ctx, SFS2D_E_NOMEM, "spectra: " + std::to_string(ngroups) + " rows of " + std::to_string(roww) +
+                                           " int64 words do not fit");
+  const int64_t words = ngroups * roww;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = CTX_STREAM(ctx);
+  if ((size_t)nsel > pl->spec_sel_cap || (!out_dev && (size_t)words > pl->spec_cap)) {
+    HIPCHK(ctx, hipStreamSynchronize(st));   // an earlier call may still read what is replaced
+    if ((size_t)nsel > pl->spec_sel_cap) {
+      hipFree(pl->d_spec_sel);
+      pl->spec_sel_cap = 0;
+      int rc = dalloc(ctx, &pl->d_spec_sel, (size_t)nsel);
+      if (rc) return rc;
+      pl->spec_sel_cap = (size_t)nsel;
+    }
+    if (!out_dev && (size_t)words > pl->spec_cap) {
+      hipFree(pl->d_spec);
+      pl->spec_cap = 0;
+      pl->spec_words = -1;
+      int rc = dalloc(ctx, &pl->d_spec, (size_t)words);
+      if (rc) {
+        (void)hipGetLastError();
+        return rc;
+      }
+      pl->spec_cap = (size_t)words;
+    }
+  }
+  int64_t* out = out_dev ? out_dev : pl->d_spec;
+  // the row's u32 histogram in LDS while a CU can hold it; above the default limit the kernels opt in, once per
+  // plan, and a refusal selects the global-atomic instantiations (as k_prep's histogram)
+  const size_t lds = sizeof(uint32_t) * (size_t)roww;
+  if (pl->spec_lds_ok < 0) {
+    pl->spec_lds_ok = lds <= 160 * 1024 ? 1 : 0;
+    if (pl->spec_lds_ok && lds > 64 * 1024 && set_max_lds<SpecWin>(lds) != hipSuccess) {
+      (void)hipGetLastError();
+      pl->spec_lds_ok = 0;
+    }
+  }
+  const bool ldsh = pl->spec_lds_ok == 1;
+  HIPCHK(ctx, hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)words, st));
+  pl->spec_last = out;
+  pl->spec_words = words;
+  if (nsel == 0) return 0;
+  HIPCHK(ctx, hipMemcpyAsync(pl->d_spec_sel, pl->spec_sel_h.data(), sizeof(SpecSel) * (size_t)nsel, hipMemcpyHostToDevice, st));
+  int rc = 0;
+  const SpecWin::Fn k = variant(ctx, SpecWin{pl->cnt, ldsh}, "k_spec_win", &rc);
+  if (!k) return rc;
+  // A contiguous run of the selection per workgroup, at most as many workgroups as are resident with the row in
+  // LDS.  Every workgroup that holds entries of a group flushes into that group's row, and a workgroup walks its
+  // entries one after another: 4,362 windows of ~358 SNPs pooled into one group took 50 us from 2,048 workgroups,
+  // 38 us from 272 and 35 us from 1,090, against 23 us each in its own row.  So no more
+  // workgroups than the selection has runs of one group -- but one per CU at least, and one per 4 entries, so that
+  // a long pooled list is still streamed by the whole chip.
+  const int per_cu = ldsh ? (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / lds)) : 8;
+  const int64_t want = std::max<int64_t>(std::max<int64_t>(ctx->ncu, nruns), nsel / 4);
+  const dim3 g((unsigned)std::min<int64_t>(nsel, std::min<int64_t>(want, (int64_t)per_cu * ctx->ncu)));
+  const sfs2d_window* recs = pl->last_out ? pl->last_out : pl->d_out;
+  hipLaunchKernelGGL(k, g, dim3(SPEC_BLOCK), ldsh ? lds : 0, st, pl->K, d->counts, scan_src(pl), recs, pl->d_spec_sel,
+                     reinterpret_cast<unsigned long long*>(out), (uint32_t)nsel, (uint32_t)pl->nrec, (uint32_t)ngroups,
+                     (uint32_t)d->n);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int sfs2d_plan_spectra_read(sfs2d_plan* pl, int64_t* out_host, int64_t cap_words, int64_t* nwords_out) {
+  if (!pl || !nwords_out) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  if (pl->spec_words < 0) return set_err(ctx, SFS2D_E_ARG, "sfs2d_plan_spectra_read before sfs2d_plan_spectra");
+  *nwords_out = pl->spec_words;
+  if (cap_words < pl->spec_words) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
+  if (pl->spec_words && !out_host) return SFS2D_E_ARG;
+  if (pl->spec_words)
+    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->spec_last, sizeof(int64_t) * (size_t)pl->spec_words, hipMemcpyDeviceToHost,
                                CTX_STREAM(ctx)));
   HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
   return 0;

@@ -30,6 +30,12 @@ def bg_row_words(n1p: int, n2p: int) -> int:
     inner 2D sum] (sfs2d_bg_hist_dev, sfs2d_plan_bg_rows_dev)."""
     return (2 * n1p + 1) * (2 * n2p + 1) + 2 * n1p + 2 * n2p + 3
 
+
+def spec_row_words(n1p: int, n2p: int) -> int:
+    """SFS2D_SPEC_ROW_WORDS: one group of window spectra as an int64 row [2D bins | pop-1 folded, n1p + 1 |
+    pop-2 folded, n2p + 1] (sfs2d_plan_spectra)."""
+    return (2 * n1p + 1) * (2 * n2p + 1) + n1p + n2p + 2
+
 # the exported symbols of include/sfs2d.h (checked by tests/test_lib_abi.py)
 EXPORTS = [
     "sfs2d_abi_version", "sfs2d_ctx_create", "sfs2d_ctx_destroy", "sfs2d_last_error", "sfs2d_ctx_set_stream",
@@ -47,6 +53,7 @@ EXPORTS = [
     "sfs2d_plan_scan_variant", "sfs2d_plan_seg_kind", "sfs2d_plan_slots_once",
     "sfs2d_plan_diversity", "sfs2d_plan_diversity_read",
     "sfs2d_plan_create_regions", "sfs2d_plan_attach_regions",
+    "sfs2d_plan_spectra", "sfs2d_plan_spectra_read",
 ]
 ABI_VERSION = 2   # SFS2D_ABI_VERSION of include/sfs2d.h
 
@@ -168,6 +175,8 @@ def lib():
     L.sfs2d_plan_null_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sfs2d_plan_diversity.argtypes = [vp, vp]
     L.sfs2d_plan_diversity_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.sfs2d_plan_spectra.argtypes = [vp, vp, vp, i64, i64, vp]
+    L.sfs2d_plan_spectra_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sfs2d_data_synth_sims.argtypes = [vp, C.POINTER(SynthParams), vp, vp, i32, vp, i32, C.POINTER(vp)]
     L.sfs2d_data_read.argtypes = [vp, vp, vp, i64]
     L.sfs2d_ctx_use_own_stream.argtypes = [vp]

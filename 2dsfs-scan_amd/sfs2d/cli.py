@@ -34,6 +34,17 @@ writes ``<prefix>_regions.csv``: a leading ``name`` column (BED column 4, else `
 usual columns in the usual order, ``window_start`` / ``window_end`` the region's 1-based inclusive bounds; one row
 per BED line in the file's order, a region without SNPs with ``snp_count`` 0 and empty fields.  ``--fst``,
 ``--diversity`` and ``--null-*`` apply to it; ``--regions`` alone scans nothing else.
+
+``--outlier-spectra KEY:Q`` (repeatable; KEY one of T2D, T1D_p1, T1D_p2, new_term_p1, new_term_p2, T2D_diff, or FST
+with ``--fst``; 0 < Q < 1) writes, for every ``--window`` / ``--snp-window`` / sliding output, the joint spectrum of
+the windows whose KEY is at or above its Q quantile, pooled on the GPU (outlier_spectra):
+``<prefix>_<size>_<KEY>_top<pct>.fs`` and ``..._background.fs`` (dadi's format; the background is the sum of the
+whole-chromosome spectra of the chromosomes holding a selected window) and ``..._residuals.csv`` (``x1, x2,
+fg_count, bg_count, fg_p, bg_p, diff, t2d_term`` for the bins where either count is non-zero).  The windows are
+chosen from the statistics with the clean None rules of the sliding scans.  ``--region-spectra`` (with
+``--regions``) writes ``<prefix>_regions_spectra.npz``: ``name``, ``sfs2d[nregions, n1 + 1, n2 + 1]``,
+``sfs1d_pop1``, ``sfs1d_pop2`` in the BED file's order -- a spectrum per gene to hand to dadi / moments /
+fastsimcoal.
 """
 from __future__ import annotations
 
@@ -118,6 +129,42 @@ def write_regions_csv(path, rows, regions, chr_ids, fst=False, pvalues=False, di
             w.writerow(row)
 
 
+# --outlier-spectra KEY: the CSV's statistic columns -> the rows' keys
+SPECTRA_KEYS = {"T2D": "T2D", "T1D_p1": "T1D_pop1", "T1D_p2": "T1D_pop2", "new_term_p1": "new_term_pop1",
+                "new_term_p2": "new_term_pop2", "T2D_diff": "T2D_diff", "FST": "FST"}
+
+
+def parse_outlier_spec(text):
+    """``KEY:Q`` -> (KEY, Q); ValueError with the reason for a malformed one."""
+    key, sep, qs = str(text).partition(":")
+    if not sep or key not in SPECTRA_KEYS:
+        raise ValueError(f"--outlier-spectra {text!r}: expected KEY:Q with KEY one of {', '.join(SPECTRA_KEYS)}")
+    try:
+        q = float(qs)
+    except ValueError:
+        q = float("nan")
+    if not 0.0 < q < 1.0:
+        raise ValueError(f"--outlier-spectra {text!r}: Q must be a number in (0, 1)")
+    return key, q
+
+
+def _fmt_pct(q: float) -> str:
+    return f"{round((1.0 - q) * 100.0, 6):g}"
+
+
+def write_outlier_spectra(stem, res, folded, pop_ids):
+    """The three files of one outlier_spectra result ``res`` under ``stem``; returns their paths."""
+    from . import spectra as SP
+    paths = [f"{stem}.fs", f"{stem}_background.fs", f"{stem}_residuals.csv"]
+    SP.write_dadi_fs(paths[0], res["foreground"], folded, pop_ids)
+    SP.write_dadi_fs(paths[1], res["background"], folded, pop_ids)
+    with open(paths[2], "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(SP.RESIDUAL_COLUMNS)
+        w.writerows(SP.residual_rows(res["residuals"]))
+    return paths
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m sfs2d", description=__doc__.split("\n\n")[0])
     ap.add_argument("vcf")
@@ -147,6 +194,11 @@ def main(argv=None):
                     help="append per-window pi, dxy, da, Watterson's theta, S and Tajima's D (twelve columns)")
     ap.add_argument("--regions", default=None, metavar="FILE.bed",
                     help="scan the intervals of a BED file as windows of their own -> <prefix>_regions.csv")
+    ap.add_argument("--outlier-spectra", action="append", default=[], metavar="KEY:Q",
+                    help="pooled joint SFS of the windows with KEY at or above its Q quantile, its background and "
+                         "their per-bin residuals -> <prefix>_<size>_<KEY>_top<pct>{.fs,_background.fs,_residuals.csv}")
+    ap.add_argument("--region-spectra", action="store_true",
+                    help="with --regions: every region's 2D and folded 1D spectra -> <prefix>_regions_spectra.npz")
     ap.add_argument("--out-prefix", default="stats")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="VCF parser threads (0 = all)")
@@ -155,6 +207,16 @@ def main(argv=None):
         a.window = [20000]
     if a.null_replicates is not None and a.null_replicates < 1:
         ap.error("--null-replicates must be >= 1")
+    ospecs = []
+    for text in a.outlier_spectra:
+        try:
+            ospecs.append(parse_outlier_spec(text))
+        except ValueError as e:
+            ap.error(str(e))
+        if ospecs[-1][0] == "FST" and not a.fst:
+            ap.error("--outlier-spectra FST:Q needs --fst")
+    if a.region_spectra and a.regions is None:
+        ap.error("--region-spectra needs --regions")
     null = a.null_replicates is not None
     block = None
     if a.null_block is not None:
@@ -208,6 +270,28 @@ def main(argv=None):
         write_regions_csv(path, res["regions"], rg, chr_ids, a.fst, null, a.diversity)
         outs.append(path)
         print(f"region_scan: {len(rg)} regions -> {path}", file=sys.stderr)
+
+    def spectra_out(size, **geometry):
+        # (the new flags alone: a scan of its own per file, nothing of the calls above changes)
+        for key, q in ospecs:
+            res = obj.outlier_spectra(packed, key=SPECTRA_KEYS[key], q=q, fst=key == "FST", **geometry)
+            stem = f"{a.out_prefix}_{size}_{key}_top{_fmt_pct(q)}"
+            outs.extend(write_outlier_spectra(stem, res, not a.no_fold, (a.pop1, a.pop2)))
+            print(f"outlier_spectra {size} {key} >= q{q:g}: {len(res['labels'])} windows, pooled T2D {res['T2D']} -> "
+                  f"{stem}.fs", file=sys.stderr)
+
+    def region_spectra_out():
+        if not a.region_spectra:
+            return
+        import numpy as np
+        sp = obj.window_spectra(packed, regions=rg)
+        keys = rg.keys()
+        path = f"{a.out_prefix}_regions_spectra.npz"
+        np.savez(path, name=np.array(keys, dtype=str), sfs2d=np.stack([sp[k]["sfs2d"] for k in keys]),
+                 sfs1d_pop1=np.stack([sp[k]["sfs1d_pop1"] for k in keys]),
+                 sfs1d_pop2=np.stack([sp[k]["sfs1d_pop2"] for k in keys]))
+        outs.append(path)
+        print(f"window_spectra: {len(keys)} regions -> {path}", file=sys.stderr)
     t = time.perf_counter()
     if a.step is not None:   # sliding windows: every size from one upload and one k_prep pass
         if null:
@@ -222,7 +306,9 @@ def main(argv=None):
             write_csv(path, rows, chr_ids, {k: r["FST"] for k, r in rows.items()} if a.fst else None, pixy, null, **dkw)
             outs.append(path)
             print(f"sliding_scan {ws} bp / {a.step} bp: {len(rows)} windows -> {path}", file=sys.stderr)
+            spectra_out(f"{_fmt_kb(ws)}_step{_fmt_kb(a.step)}", window_size=ws, step_size=a.step)
         regions_out(res)
+        region_spectra_out()
         return outs
     # every window size from one k_prep pass over the resident stream (sfs2d_plan_attach)
     if null:
@@ -236,6 +322,7 @@ def main(argv=None):
         write_csv(path, res[ws], chr_ids, res["fst"][ws] if a.fst else None, pixy, null, **dkw)
         outs.append(path)
         print(f"combined_scan {ws} bp: {len(res[ws])} windows -> {path}", file=sys.stderr)
+        spectra_out(_fmt_kb(ws), window_size=ws)
     for S in a.snp_window:
         stats = res[f"{S}snps"]
         fst = obj.window_fst(packed, snp_window_size=S) if a.fst else None
@@ -243,7 +330,9 @@ def main(argv=None):
         write_csv(path, stats, chr_ids, fst, pixy, null, **dkw)
         outs.append(path)
         print(f"scan_perChr_bySNPs {S} SNPs: {len(stats)} windows -> {path}", file=sys.stderr)
+        spectra_out(f"{S}snps", snp_window_size=S)
     regions_out(res)
+    region_spectra_out()
     return outs
 
 

@@ -365,6 +365,37 @@ class Plan:
                                                               C.byref(n)))
         return out
 
+    def spectra(self, rec=None, grp=None, ngroups: Optional[int] = None,
+                out_dev_ptr: Optional[int] = None) -> Optional[np.ndarray]:
+        """The spectra themselves of chosen records of this plan's last run, summed into groups
+        (sfs2d_plan_spectra): an ``int64[ngroups, L.spec_row_words(n1p, n2p)]`` array, row g laid out [2D grid,
+        row-major | pop-1 folded 1D, n1p + 1 | pop-2 folded 1D, n2p + 1] (sfs2d.spectra.split_row takes it apart)
+        and summed over the entries i with ``grp[i] == g`` of the records ``rec[i]``.  ``rec`` None: every record
+        in order; then ``grp`` None: one group per record.  ``ngroups`` None: the record count, or with ``grp``
+        its largest entry + 1.  A record listed twice is counted twice; on overlapping windows a group is the sum
+        over its windows, not the spectrum of their union.  Any plan that has run, attached plans included.  With
+        ``out_dev_ptr`` (a device buffer of ngroups rows) nothing is copied to the host and None is returned."""
+        r = None if rec is None else np.ascontiguousarray(np.asarray(rec, np.int64).reshape(-1))
+        g = None if grp is None else np.ascontiguousarray(np.asarray(grp, np.int32).reshape(-1))
+        if r is not None and g is not None and len(r) != len(g):
+            raise ValueError("spectra: rec and grp differ in length")
+        nsel = len(r) if r is not None else (len(g) if g is not None else self.nrec)
+        if ngroups is None:
+            ngroups = max(1, self.nrec if g is None else (int(g.max()) + 1 if len(g) else 1))
+        ngroups = int(ngroups)
+        # (an empty array still passes a non-null pointer: a NULL means "every record" / "group i = record i")
+        rp = None if r is None else C.c_void_p(r.ctypes.data)
+        gp = None if g is None else C.c_void_p(g.ctypes.data)
+        self.eng.check(self.eng.lib.sfs2d_plan_spectra(self.h, rp, gp, nsel, ngroups,
+                                                       C.c_void_p(out_dev_ptr) if out_dev_ptr else None))
+        if out_dev_ptr:
+            return None
+        roww = L.spec_row_words(self.cfg.n1p, self.cfg.n2p)
+        out = np.zeros((ngroups, roww), np.int64)
+        n = C.c_int64()
+        self.eng.check(self.eng.lib.sfs2d_plan_spectra_read(self.h, L.ptr(out), out.size, C.byref(n)))
+        return out
+
     def bg_buffer(self):
         p = C.c_void_p()
         nb = C.c_int64()

@@ -1,0 +1,241 @@
+"""Window spectra: the joint SFS of chosen windows, pooled or each, and what to do with them.
+
+The GPU (k_spec_win, csrc/sfs2d_spec.hpp; ``Plan.spectra``) sums the 2D and folded 1D spectra of chosen records of
+a plan's last run into groups (include/sfs2d.h, ``sfs2d_plan_spectra``).  This module holds
+what is left for the host: taking a group's row apart (``split_row``), the numpy twin of the device sums
+(``window_spectra_np``, the definition the tests compare against), choosing the outlier windows of a scan
+(``select_top``), the per-bin comparison of a pooled foreground with its background (``residuals``) and dadi's
+``.fs`` file format (``write_dadi_fs`` / ``read_dadi_fs``).
+
+Per record with SNP range [begin, end), under the plan's position filter, variant_type filter and fold:
+
+* 2D: the dense (2 n1p + 1) x (2 n2p + 1) grid of calculate_2d_sfs over the window, row-major (x1, x2); bin (0, 0)
+  is 0 (those SNPs are skipped), the last bin (n1, n2) is counted;
+* 1D, per population: the folded spectrum of raw alt counts at the inner bins 1 .. pop_size - 1 (the bins T1D
+  reads); entries 0 and pop_size are 0.
+
+A group is the SUM over its selection entries.  On overlapping windows (sliding windows, regions) that is a sum
+over windows, not the spectrum of their union: a SNP inside two selected windows is counted twice.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import _lib as L
+from .diversity import _filter_mask
+
+__all__ = ["split_row", "window_spectra_np", "select_top", "residuals", "pooled_t2d", "write_dadi_fs",
+           "read_dadi_fs", "RESIDUAL_COLUMNS"]
+
+RESIDUAL_COLUMNS = ["x1", "x2", "fg_count", "bg_count", "fg_p", "bg_p", "diff", "t2d_term"]
+
+
+def split_row(row, n1p: int, n2p: int):
+    """(grid, folded1, folded2) of one group row [2D bins | pop-1 folded, n1p + 1 | pop-2 folded, n2p + 1]:
+    the (2 n1p + 1, 2 n2p + 1) grid and the two folded 1D spectra (views of ``row``)."""
+    row = np.asarray(row)
+    g1, g2 = 2 * n1p + 1, 2 * n2p + 1
+    nb2 = g1 * g2
+    if row.ndim != 1 or row.size != L.spec_row_words(n1p, n2p):
+        raise ValueError(f"a spectra row of pop sizes ({n1p}, {n2p}) has {L.spec_row_words(n1p, n2p)} words")
+    return row[:nb2].reshape(g1, g2), row[nb2:nb2 + n1p + 1], row[nb2 + n1p + 1:]
+
+
+def _record_row(p, lo, hi, cfg, n1p, n2p, fold):
+    n1, n2 = 2 * n1p, 2 * n2p
+    row = np.zeros(L.spec_row_words(n1p, n2p), np.int64)
+    if hi <= lo:
+        return row
+    m = _filter_mask(p, lo, hi, cfg)
+    c = p.counts[lo:hi][m]
+    r1, a1, r2, a2 = [((c >> np.uint32(s)) & np.uint32(0xFF)).astype(np.int64) for s in (0, 8, 16, 24)]
+    x1, x2 = a1, a2
+    if fold:   # the joint fold on the SNP's own counts; a tie is not folded
+        sw = (a1 + a2) > (n1p + n2p)
+        x1, x2 = np.where(sw, r1, a1), np.where(sw, r2, a2)
+    keep = (x1 != 0) | (x2 != 0)
+    x1, x2 = x1[keep], x2[keep]
+    if x1.size and (x1.max() > n1 or x2.max() > n2):
+        raise ValueError("2D SFS bin outside the grid (allele counts exceed the declared sample size)")
+    nb2 = (n1 + 1) * (n2 + 1)
+    row[:nb2] = np.bincount(x1 * (n2 + 1) + x2, minlength=nb2)
+    off = nb2
+    for a, npop in ((a1, n1p), (a2, n2p)):
+        a = a[a != 0]
+        if a.size and a.max() > 2 * npop:
+            raise KeyError(int(a.max()))
+        f = np.minimum(a, 2 * npop - a)
+        f = f[(f >= 1) & (f <= npop - 1)]
+        row[off:off + npop + 1] = np.bincount(f, minlength=npop + 1)
+        off += npop + 1
+    return row
+
+
+def window_spectra_np(p, recs, cfg, rec=None, grp=None, ngroups=None) -> np.ndarray:
+    """The numpy twin of ``Plan.spectra``: ``int64[ngroups, row words]`` from the packed SNPs ``p``, the plan's
+    window records ``recs`` and its configuration ``cfg`` (a ScanConfig, or an object with pop sizes ``n1p`` /
+    ``n2p``, ``fold``, the position filter and ``variant_type``), with ``rec`` / ``grp`` / ``ngroups`` as
+    ``Plan.spectra`` takes them."""
+    n1p, n2p, fold = int(cfg.n1p), int(cfg.n2p), bool(cfg.fold)
+    nrec = len(recs)
+    rec = np.arange(nrec, dtype=np.int64) if rec is None else np.asarray(rec, np.int64).reshape(-1)
+    grp = np.arange(len(rec), dtype=np.int64) if grp is None else np.asarray(grp, np.int64).reshape(-1)
+    if len(rec) != len(grp):
+        raise ValueError("rec and grp differ in length")
+    if ngroups is None:
+        ngroups = max(1, int(grp.max()) + 1 if len(grp) else 1)
+    out = np.zeros((int(ngroups), L.spec_row_words(n1p, n2p)), np.int64)
+    cache = {}
+    for s, g in zip(rec.tolist(), grp.tolist()):
+        if not 0 <= s < nrec or not 0 <= g < ngroups:
+            raise ValueError(f"entry (record {s}, group {g}) out of range")
+        r = recs[s]
+        if int(r["flags"]) & (L.W_EMPTY | L.W_EXTRA):
+            continue
+        if s not in cache:
+            hi = min(int(r["end"]), p.n)
+            cache[s] = _record_row(p, min(int(r["begin"]), hi), hi, cfg, n1p, n2p, fold)
+        out[g] += cache[s]
+    return out
+
+
+def select_top(rows: dict, key: str, q: float):
+    """The labels of the rows of a scan's result dict whose ``key`` lies in the top 1 - q of its values, in scan
+    order: candidates are the rows whose value is neither None nor NaN (+inf is kept: such a window is the most
+    extreme there is), the threshold is ``numpy.quantile(values, q, method="higher")`` -- a value of the sample
+    -- and a row is selected when its value >= the threshold (ties at the threshold are all in).  ValueError: q
+    outside (0, 1), or no candidate."""
+    q = float(q)
+    if not 0.0 < q < 1.0:
+        raise ValueError(f"select_top: q must lie in (0, 1), got {q}")
+    cand = []
+    for lb, row in rows.items():
+        v = row.get(key)
+        if v is None:
+            continue
+        v = float(v)
+        if math.isnan(v):
+            continue
+        cand.append((lb, v))
+    if not cand:
+        raise ValueError(f"select_top: no row has a value of {key!r}")
+    thr = float(np.quantile(np.array([v for _, v in cand], np.float64), q, method="higher"))
+    return [lb for lb, v in cand if v >= thr]
+
+
+def residuals(fg_grid, bg_grid) -> dict:
+    """Per bin of the grid, a pooled foreground against its background: the two proportions over the inner bins
+    (``ravel()[1:-1]``, the sum normalize_2d_sfs divides by), their difference, and the bin's term of T2D,
+    ``2 x (ln(x / N) - ln(b / B))`` -- 0 where x = 0, +inf where x > 0 and b = 0; the terms sum to the pooled T2D
+    (the multinomial coefficients of the two likelihoods cancel).  Returns a dict of arrays shaped like the grid:
+    ``fg_count``, ``bg_count``, ``fg_p``, ``bg_p``, ``diff``, ``t2d_term``; the first and the last bin, which the
+    statistic does not read, have proportions of their own counts over the same sums and a term of 0.  With an
+    empty foreground or background (N = 0 or B = 0) the proportions over it and the terms are NaN."""
+    fg = np.asarray(fg_grid)
+    bg = np.asarray(bg_grid)
+    if fg.shape != bg.shape or fg.ndim != 2:
+        raise ValueError("residuals: two grids of one shape")
+    x = fg.astype(np.float64).ravel()
+    b = bg.astype(np.float64).ravel()
+    N, B = math.fsum(x[1:-1].tolist()), math.fsum(b[1:-1].tolist())
+    nan = np.full(x.shape, np.nan)
+    fp = x / N if N > 0 else nan.copy()
+    bp = b / B if B > 0 else nan.copy()
+    term = nan.copy()
+    if N > 0 and B > 0:
+        term = np.zeros_like(x)
+        inner = np.zeros(x.shape, bool)
+        inner[1:-1] = True
+        pos = inner & (x > 0)
+        hit = pos & (b > 0)
+        term[hit] = 2.0 * x[hit] * (np.log(fp[hit]) - np.log(bp[hit]))
+        term[pos & ~(b > 0)] = np.inf
+    sh = fg.shape
+    return {"fg_count": fg.copy(), "bg_count": bg.copy(), "fg_p": fp.reshape(sh), "bg_p": bp.reshape(sh),
+            "diff": (fp - bp).reshape(sh), "t2d_term": term.reshape(sh)}
+
+
+def pooled_t2d(res: dict):
+    """T2D of the pooled foreground against the background: the sum of ``residuals``' terms (None when either is
+    empty)."""
+    t = res["t2d_term"].ravel()
+    if np.isnan(t).any():
+        return None
+    return math.inf if np.isinf(t).any() else math.fsum(t.tolist())
+
+
+def residual_rows(res: dict):
+    """The rows of the residual table, RESIDUAL_COLUMNS each: the bins where either count is non-zero, row-major."""
+    fg, bg = res["fg_count"], res["bg_count"]
+    out = []
+    for i, j in zip(*np.nonzero((fg != 0) | (bg != 0))):
+        out.append([int(i), int(j), int(fg[i, j]), bg[i, j].item(), float(res["fg_p"][i, j]), float(res["bg_p"][i, j]),
+                    float(res["diff"][i, j]), float(res["t2d_term"][i, j])])
+    return out
+
+
+def _fs_mask(d1: int, d2: int, folded: bool) -> np.ndarray:
+    m = np.zeros((d1, d2), np.int64)
+    m[0, 0] = m[d1 - 1, d2 - 1] = 1
+    if folded:   # (n1 + n2) / 2 = n1p + n2p: the bins a folded spectrum cannot hold
+        i, j = np.indices((d1, d2))
+        m[i + j > (d1 - 1 + d2 - 1) // 2] = 1
+    return m
+
+
+def _fs_num(v) -> str:
+    v = v.item() if hasattr(v, "item") else v
+    return str(int(v)) if isinstance(v, (int, np.integer)) or float(v).is_integer() else repr(float(v))
+
+
+def write_dadi_fs(path, grid, folded: bool, pop_ids=("pop1", "pop2")):
+    """Write the 2D spectrum ``grid`` as a dadi ``.fs`` file (dadi.Spectrum.from_file reads it; moments too): three
+    lines -- ``D1 D2 folded|unfolded "pop1" "pop2"``, the values row-major, the mask (1 = masked) at (0, 0), at
+    (n1, n2) and, when ``folded``, where i + j > n1p + n2p."""
+    g = np.asarray(grid)
+    if g.ndim != 2:
+        raise ValueError("write_dadi_fs: a 2D grid")
+    if len(pop_ids) != 2 or any('"' in str(s) or "\n" in str(s) for s in pop_ids):
+        raise ValueError("write_dadi_fs: two population ids without quotes or line breaks")
+    d1, d2 = g.shape
+    with open(path, "w") as f:
+        f.write(f'{d1} {d2} {"folded" if folded else "unfolded"} "{pop_ids[0]}" "{pop_ids[1]}"\n')
+        f.write(" ".join(_fs_num(v) for v in g.ravel()) + "\n")
+        f.write(" ".join(str(int(v)) for v in _fs_mask(d1, d2, bool(folded)).ravel()) + "\n")
+
+
+def read_dadi_fs(path):
+    """Read a 2D ``.fs`` file: (grid, folded, pop_ids, mask).  ``grid`` is int64 when every value is an integer,
+    else float64; comment lines (#) ahead of the header are skipped; ``mask`` is None when the file has no mask
+    line."""
+    with open(path) as f:
+        lines = [ln.strip() for ln in f]
+    lines = [ln for ln in lines if ln and not ln.startswith("#")]
+    if len(lines) < 2:
+        raise ValueError(f"{path}: not a dadi .fs file (header and values expected)")
+    head, _, rest = lines[0].partition('"')
+    tok = head.split()
+    if len(tok) < 2:
+        raise ValueError(f"{path}: header without two dimensions")
+    dims, flags = [], []
+    for t in tok:
+        (dims if t.isdigit() else flags).append(t)
+    if len(dims) != 2:
+        raise ValueError(f"{path}: {len(dims)} dimensions (a 2D spectrum expected)")
+    d1, d2 = int(dims[0]), int(dims[1])
+    folded = "folded" in flags
+    ids = ('"' + rest).split('"')[1::2] if rest else []
+    vals = lines[1].split()
+    if len(vals) != d1 * d2:
+        raise ValueError(f"{path}: {len(vals)} values for a {d1} x {d2} grid")
+    fv = np.array([float(v) for v in vals], np.float64)
+    grid = fv.astype(np.int64) if np.all(np.isfinite(fv)) and np.all(fv == np.floor(fv)) else fv
+    mask = None
+    if len(lines) > 2:
+        mv = lines[2].split()
+        if len(mv) != d1 * d2:
+            raise ValueError(f"{path}: {len(mv)} mask entries for a {d1} x {d2} grid")
+        mask = np.array([int(v) for v in mv], np.int64).reshape(d1, d2)
+    return grid.reshape(d1, d2), folded, tuple(ids), mask

@@ -786,6 +786,149 @@ class LikelihoodInference_jointSFS:
             dev.close()
         return DV.rows(recs, div, p, w, "bp" if bp else "snps", step, (self.pop1_size, self.pop2_size))
 
+    # ------------------------------------------------------------------ window spectra (extension)
+    def _no_distributed_spectra(self, what):
+        if self.distributed:
+            raise NotImplementedError(f"{what} is single-GPU (distributed sharding of the window spectra is not implemented)")
+
+    def _spectra_cfg(self, p, window_size, snp_window_size, step_size, regions, **kw):
+        """(cfg, kind, w, step, Regions) of the one window geometry given."""
+        given = [x is not None for x in (window_size, snp_window_size, regions)]
+        if sum(given) != 1:
+            raise ValueError("give exactly one of window_size / snp_window_size / regions")
+        if step_size is not None and window_size is None:
+            raise ValueError("step_size applies to fixed-bp windows: give window_size")
+        if regions is not None:
+            rg = self._regions_of(p, regions)
+            return self._cfg(p, window_mode=L.WINDOW_BP, regions=rg, **kw), "regions", None, None, rg
+        bp = window_size is not None
+        w = int(window_size if bp else snp_window_size)
+        step = None if step_size is None else self._check_steps([w], step_size)
+        cfg = self._cfg(p, window_mode=L.WINDOW_BP if bp else L.WINDOW_SNPS, window=w, step=step, **kw)
+        return cfg, "bp" if bp else "snps", w, step, None
+
+    def window_spectra(self, data_dict, window_size=None, snp_window_size=None, step_size=None, regions=None,
+                       select=None):
+        """The spectra themselves of a scan's windows, where the scans return them reduced to T2D / T1D:
+        {label: {"sfs2d": int64 grid (2 pop1_size + 1, 2 pop2_size + 1), "sfs1d_pop1", "sfs1d_pop2": folded 1D
+        spectra}}, labels as combined_scan (``window_size``; sliding_scan with ``step_size``), scan_perChr_bySNPs
+        (``snp_window_size``) or region_scan (``regions``: one entry per region, an empty region all zero) emit them.
+        ``select``: a list of those labels (None: every window), one entry each, in that order.  The grid is
+        calculate_2d_sfs over the window under the object's filters and fold -- bin (0, 0) is 0, the last bin is
+        counted; the 1D spectra hold the inner bins 1 .. pop_size - 1 that T1D reads, entries 0 and pop_size are 0.
+        Summed on the GPU from the data the scan holds (k_spec_win).  The
+        reference cuts the windows' SNPs into new VCFs and reads them again (sims_scan.py:726-936)."""
+        self._no_distributed_spectra("window_spectra")
+        p = self._pack(data_dict)
+        cfg, kind, w, step, rg = self._spectra_cfg(p, window_size, snp_window_size, step_size, regions,
+                                                   bg_mode=L.BG_PER_CHROM)
+        from sfs2d import spectra as SP
+        eng = self._engine()
+        dev = eng.upload(p)
+        try:
+            pl = eng.plan(dev, cfg)
+            try:
+                pl.run()
+                pl.check()
+                recs = pl.read()
+                if rg is not None:   # (every region has an entry, in the caller's order)
+                    index = {k: int(s) for k, s in zip(rg.keys(), rg.slot.tolist())}
+                else:
+                    index = {lb: i for i, lb in enumerate(post.record_labels(recs, p, kind, w, step)) if lb is not None}
+                labels = list(index) if select is None else list(select)
+                for lb in labels:
+                    if lb not in index:
+                        raise ValueError(f"window_spectra: no window labelled {lb!r}")
+                rows = pl.spectra([index[lb] for lb in labels], np.arange(len(labels), dtype=np.int32),
+                                  max(1, len(labels)))
+            finally:
+                pl.close()
+        finally:
+            dev.close()
+        out = {}
+        for lb, row in zip(labels, rows):
+            g, f1, f2 = SP.split_row(row, self.pop1_size, self.pop2_size)
+            out[lb] = {"sfs2d": g.copy(), "sfs1d_pop1": f1.copy(), "sfs1d_pop2": f2.copy()}
+        return out
+
+    @staticmethod
+    def _clean_rows(recs, labels, fst=None):
+        """{label: combined_scan's seven keys (+ "FST")} of the labelled records, with sliding_scan's clean None
+        rules (no stale carry, no final block, no TypeError)."""
+        rows = {}
+        for i, (r, lb) in enumerate(zip(recs, labels)):
+            if lb is None:
+                continue
+            T2D, T1, T2 = post._v(r, 2), post._v(r, 1), post._v(r, 0)
+            row = {"snp_count": int(r["snp_count"]), "T2D": T2D, "T1D_pop1": T1, "T1D_pop2": T2,
+                   "new_term_pop1": None if T2D is None or T1 is None else T2D - T1,
+                   "new_term_pop2": None if T2D is None or T2 is None else T2D - T2,
+                   "T2D_diff": None if T2D is None or T1 is None or T2 is None else T2D - (T1 + T2) / 2}
+            if fst is not None:
+                row["FST"] = None if i >= len(fst) or np.isnan(fst[i]) else float(fst[i])
+            rows[lb] = row
+        return rows
+
+    def outlier_spectra(self, data_dict, window_size=None, key="T2D", q=0.99, fst=False, snp_window_size=None,
+                        step_size=None, background_chromosome=None):
+        """The joint spectrum of a scan's outlier windows beside its background, and which bins drive T2D: the
+        windows whose ``key`` (T2D, T1D_pop1, T1D_pop2, new_term_pop1, new_term_pop2, T2D_diff, snp_count; or FST
+        with ``fst``) is in the top 1 - ``q`` of the scan (sfs2d.spectra.select_top: value >= the ``q`` quantile
+        of the windows that have one; the statistics with sliding_scan's clean None rules), pooled into ONE
+        spectrum on the GPU from the data the scan holds.  Windows as in ``window_spectra`` (``window_size``,
+        with ``step_size`` sliding; or ``snp_window_size``); ``background_chromosome`` as in sliding_scan.
+        Returns {"labels": the selected labels in scan order, "foreground": the pooled int64 grid,
+        "sfs1d_pop1" / "sfs1d_pop2": the pooled folded 1D spectra, "background": the pooled background grid --
+        the sum of the whole-chromosome grids of the chromosomes that hold a selected window, or
+        ``background_chromosome``'s --, "background_chromosomes": their names, "residuals":
+        sfs2d.spectra.residuals(foreground, background), "T2D": the pooled foreground's T2D against that
+        background (the sum of the residual terms; None when either is empty)}.  On sliding windows the pool is a
+        sum over windows, not the spectrum of their union: a SNP in two selected windows is counted twice.  The
+        reference merges the outlier windows' VCFs with an outside tool, reads them again and subtracts the
+        normalised spectra (sims_scan.py:726-936)."""
+        self._no_distributed_spectra("outlier_spectra")
+        if key == "FST" and not fst:
+            raise ValueError("key 'FST' needs fst=True")
+        p = self._pack(data_dict)
+        bg = None
+        if background_chromosome is not None:
+            if background_chromosome not in p.chrom_names:
+                raise ValueError(f"Background chromosome {background_chromosome} not found in the data.")
+            bg = self._bg_arrays(p, p.chrom_names.index(background_chromosome))
+        cfg, kind, w, step, _ = self._spectra_cfg(p, window_size, snp_window_size, step_size, None, fst=bool(fst),
+                                                  bg_mode=L.BG_PER_CHROM if bg is None else L.BG_SUPPLIED)
+        from sfs2d import spectra as SP
+        eng = self._engine()
+        dev = eng.upload(p)
+        try:
+            pl = eng.plan(dev, cfg)
+            try:
+                if bg is not None:
+                    pl.set_background(*bg)
+                pl.run()
+                pl.check()
+                recs = pl.read()
+                labels = post.record_labels(recs, p, kind, w, step)
+                rows = self._clean_rows(recs, labels, pl.read_fst() if fst else None)
+                top = SP.select_top(rows, key, q)
+                index = {lb: i for i, lb in enumerate(labels) if lb is not None}
+                sel = [index[lb] for lb in top]
+                row = pl.spectra(sel, np.zeros(len(sel), np.int32), 1)[0]
+                if bg is not None:
+                    bg_grid, bg_names = np.asarray(bg[0], np.int64), [background_chromosome]
+                else:
+                    chroms = sorted(set(int(recs[i]["chrom"]) for i in sel))
+                    bg_names = [p.chrom_names[c] for c in chroms]
+                    bg_grid = sum(np.asarray(eng.bg_hist(dev, cfg, c)[0], np.int64) for c in chroms)
+            finally:
+                pl.close()
+        finally:
+            dev.close()
+        g, f1, f2 = SP.split_row(row, self.pop1_size, self.pop2_size)
+        res = SP.residuals(g, bg_grid)
+        return {"labels": top, "foreground": g.copy(), "sfs1d_pop1": f1.copy(), "sfs1d_pop2": f2.copy(),
+                "background": bg_grid, "background_chromosomes": bg_names, "residuals": res, "T2D": SP.pooled_t2d(res)}
+
     # ------------------------------------------------------------------ SFS primitives
     def calculate_2d_sfs(self, data_dict):
         """2D SFS dict over the grid (140-232), accumulated on the GPU (distributed: every rank a slice

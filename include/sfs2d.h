@@ -40,7 +40,8 @@ extern "C" {
  * (additive: sfs2d_params keeps its layout, the step is an argument); sfs2d_plan_null_run / _null_read added
  * (additive); sfs2d_plan_null_run_blocks added (additive: sfs2d_null_params keeps its layout, the block length is
  * an argument); sfs2d_plan_diversity / _diversity_read and sfs2d_diversity added (additive);
- * sfs2d_plan_create_regions / sfs2d_plan_attach_regions added (additive: the intervals are arguments) */
+ * sfs2d_plan_create_regions / sfs2d_plan_attach_regions added (additive: the intervals are arguments);
+ * sfs2d_plan_spectra / _spectra_read added (additive) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -371,6 +372,37 @@ int sfs2d_plan_diversity(sfs2d_plan* plan, sfs2d_diversity* out_dev);
 /* copy the last sfs2d_plan_diversity call's records to host (synchronises); SFS2D_E_CAP: cap below the record
  * count (*nrec_out holds it); SFS2D_E_ARG: no diversity call since the plan was created */
 int sfs2d_plan_diversity_read(sfs2d_plan* plan, sfs2d_diversity* out_host, int64_t cap, int64_t* nrec_out);
+/* Window spectra: the joint and folded 1D spectra themselves of chosen records of the plan's
+ * last run, summed into groups -- what the scan reduces to T2D / T1D and four totals per window, as the x_k.  For
+ * a record with SNP range [begin, end) (clamped to the data set's SNP count), under the plan's position filter,
+ * variant_type filter and fold:
+ *   2D   the dense (2 n1p + 1) x (2 n2p + 1) grid of calculate_2d_sfs over the window, row-major (x1, x2); bin (0, 0)
+ *        is 0 (the reference skips those SNPs), the last bin (n1, n2) is counted
+ *   1D   per population the folded spectrum of raw alt counts at the inner bins 1 .. pop_size - 1, the bins T1D
+ *        reads; entries 0 and pop_size are 0
+ * A group's row is SFS2D_SPEC_ROW_WORDS int64, laid out [2D bins | pop-1 folded, n1p + 1 | pop-2 folded, n2p + 1],
+ * the sum over the group's selection entries: a record listed twice is counted twice, a group with no entry is all
+ * 0, entries that name an SFS2D_W_EMPTY or SFS2D_W_EXTRA record add nothing.  On overlapping windows (sliding,
+ * regions) a group is the SUM over its windows, not the spectrum of their union: a SNP in two selected windows is
+ * counted twice.
+ * rec / grp: nsel (record index, group) pairs, HOST arrays copied to the device by the call, in any order
+ * (consecutive entries of one group are cheapest).  rec == NULL with nsel == sfs2d_plan_num_records: every record in
+ * order; then grp == NULL: group i = record i.  out_dev: ngroups rows on the device (NULL = plan-owned, read with
+ * sfs2d_plan_spectra_read), zeroed by the call.  Enqueued on the ctx stream after the plan's last run; any plan that
+ * has run, attached, sliding, regions and SNP-count plans included (their own records, the base's data and bins).
+ * Reads the records, the counts and (filtered plans) the per-SNP bins, writes out_dev alone: a following run, null
+ * run or diversity call finds everything as it was.  Integer sums: two calls give byte-equal rows.
+ * SFS2D_E_ARG, the reason in sfs2d_last_error: a plan that has not run, nsel < 0, ngroups < 1, a record index
+ * outside [0, nrec), a group outside [0, ngroups), grp == NULL with rec != NULL, rec == NULL with nsel != nrec;
+ * SFS2D_E_NOMEM: ngroups rows do not fit.
+ * The reference merges the outlier windows' SNPs into new VCFs with an outside tool and runs calculate_2d_sfs on
+ * them again (sims_scan.py:726-936). */
+#define SFS2D_SPEC_ROW_WORDS(n1p, n2p) ((2 * (n1p) + 1) * (2 * (n2p) + 1) + (n1p) + (n2p) + 2)
+int sfs2d_plan_spectra(sfs2d_plan* plan, const int64_t* rec, const int32_t* grp, int64_t nsel, int64_t ngroups,
+                       int64_t* out_dev);
+/* copy the last sfs2d_plan_spectra call's rows to host (synchronises); *nwords_out: ngroups x row words;
+ * SFS2D_E_CAP: cap_words below it; SFS2D_E_ARG: no spectra call since the plan was created */
+int sfs2d_plan_spectra_read(sfs2d_plan* plan, int64_t* out_host, int64_t cap_words, int64_t* nwords_out);
 /* launch geometry (threads per grid) of k_prep and of the scan kernel: matches the Grid_Size column
  * of rocprofv3 kernel traces, so profiles can be joined to a plan */
 int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* scan_threads);
