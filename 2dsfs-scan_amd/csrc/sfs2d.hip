@@ -14,6 +14,8 @@
 // Watterson and Tajima sums from the resident counts; it writes its own output alone.
 // sfs2d_plan_spectra enqueues k_spec_win (sfs2d_spec.hpp) over chosen records of the run: their 2D and folded 1D
 // spectra themselves, summed into groups, as int64 rows; it too writes its own output alone.
+// sfs2d_plan_project enqueues k_proj_win (sfs2d_proj.hpp) over chosen records or whole chromosomes: the joint
+// spectrum projected down to a common sample size, as int64 fixed-point rows; it writes its own output alone.
 // All device state a run touches (slot table, background replicas and counters, LDS) is left
 // zeroed by the run itself, so plans replay without memsets.
 #include <hip/hip_runtime.h>
@@ -26,8 +28,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <mutex>
+#include <new>
 #include <utility>
 #include <vector>
 
@@ -35,6 +39,7 @@
 #include "sfs2d_kernels.hpp"
 #include "sfs2d_div.hpp"
 #include "sfs2d_spec.hpp"
+#include "sfs2d_proj.hpp"
 
 using namespace sfs2dk;
 
@@ -107,6 +112,7 @@ struct sfs2d_ctx {
   hipStream_t stream = nullptr;
   double* d_lnx = nullptr;
   double* d_df = nullptr;   // D(r), F(x) (LNT each), then (1/k, 1/(k(k-1))) pairs (RCPN)
+  double* d_lf = nullptr;   // ln k!, k < PROJ_LF: k_proj_win's weights (allocated by the first sfs2d_plan_project)
   double* d_hw = nullptr;   // 1 / h(n), h(n) = sum_{i=1}^{n-1} 1/i, for n < RCPN (0 below n = 2): k_div_win's Watterson terms
   hipEvent_t stagger = nullptr;   // sfs2d_plan_run_streams: the first run's k_prep, awaited by the second stream
   std::string err;
@@ -265,6 +271,16 @@ struct sfs2d_plan {
   const int64_t* spec_last = nullptr;
   int64_t spec_words = -1;               // words of the last call (-1: none yet)
   int spec_lds_ok = -1;                  // the row's LDS histogram: -1 not asked yet, 1 granted, 0 refused (global atomics)
+  // projected window spectra (sfs2d_plan_project): as the spectra's, and the last call's shape and fixed point
+  std::vector<ProjSel> proj_sel_h;
+  ProjSel* d_proj_sel = nullptr;
+  size_t proj_sel_cap = 0;
+  int64_t* d_proj = nullptr;             // plan-owned rows (out_dev == NULL)
+  size_t proj_cap = 0;                   // ... in int64 words
+  const int64_t* proj_last = nullptr;
+  int64_t proj_groups = -1, proj_roww = 0;   // groups and row words of the last call (-1: none yet)
+  int proj_e = 0;                        // its fixed point 2^-e
+  int64_t maxsnp = 0;                    // plan_create's bound on the SNPs of one record (Fst's e, P16)
   uint64_t null_tab_runs = ~0ull;        // fused / sliced plans: the run whose tables of EVERY chromosome are in
                                          // d_tab / d_lp / d_head (their scans keep all but one chromosome's in LDS)
 };
@@ -313,6 +329,7 @@ void plan_free(sfs2d_plan* p) {
   hipFree(p->d_out); hipFree(p->d_err); hipFree(p->d_bins); hipFree(p->d_fst_own); hipFree(p->d_fsum); hipFree(p->d_gscr);
   hipFree(p->d_ntask); hipFree(p->d_null); hipFree(p->d_div);
   hipFree(p->d_spec_sel); hipFree(p->d_spec);
+  hipFree(p->d_proj_sel); hipFree(p->d_proj);
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->tev) if (e) hipEventDestroy(e);
 }
@@ -411,6 +428,16 @@ struct SpecWin {   // k_spec_win<CNT, LDSH>
   static constexpr SpecWin at(int i) { return {bool(i & 1), bool(i & 2)}; }
   constexpr bool legal() const { return true; }
   template <int I> static constexpr Fn kernel() { constexpr SpecWin s = at(I); return k_spec_win<s.cnt, s.ldsh>; }
+};
+
+struct ProjWin {   // k_proj_win<CNT, LDSH>
+  bool cnt, ldsh;
+  using Fn = decltype(&k_proj_win<true, true>);
+  static constexpr int N = 4;
+  constexpr int index() const { return cnt | ldsh << 1; }
+  static constexpr ProjWin at(int i) { return {bool(i & 1), bool(i & 2)}; }
+  constexpr bool legal() const { return true; }
+  template <int I> static constexpr Fn kernel() { constexpr ProjWin s = at(I); return k_proj_win<s.cnt, s.ldsh>; }
 };
 
 // entry I of family S's table: its kernel, instantiated only where the selection is legal
@@ -768,6 +795,7 @@ int sfs2d_ctx_destroy(sfs2d_ctx* ctx) {
   hipFree(ctx->d_lnx);
   hipFree(ctx->d_df);
   hipFree(ctx->d_hw);
+  hipFree(ctx->d_lf);
   if (ctx->stagger) hipEventDestroy(ctx->stagger);
   hipStreamDestroy(ctx->own);
   delete ctx;
@@ -1318,6 +1346,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     p16_ok = false;
   }
   pl->p16 = p16_ok;
+  pl->maxsnp = maxsnp;
   {
     // Fst fixed point 2^e: maxsnp terms of |x| <= 1 stay below 2^62 (e = 46 for 20 kb windows)
     int b = 0;
@@ -2475,6 +2504,207 @@ int sfs2d_plan_spectra_read(sfs2d_plan* pl, int64_t* out_host, int64_t cap_words
     HIPCHK(ctx, hipMemcpyAsync(out_host, pl->spec_last, sizeof(int64_t) * (size_t)pl->spec_words, hipMemcpyDeviceToHost,
                                CTX_STREAM(ctx)));
   HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------ projected window spectra
+
+namespace {
+// ln k! for k < PROJ_LF: ascending sums of ln k in long double, rounded once (lf[0] = lf[1] = 0 exactly)
+const double* proj_lf_table() {
+  static const std::array<double, PROJ_LF> t = [] {
+    std::array<double, PROJ_LF> a{};
+    long double s = 0.0L;
+    for (int k = 2; k < PROJ_LF; ++k) {
+      s += std::log((long double)k);
+      a[(size_t)k] = (double)s;
+    }
+    return a;
+  }();
+  return t.data();
+}
+}  // namespace
+
+int sfs2d_project_weights(int32_t n, int32_t a, int32_t m, double* w_out) {
+  if (!w_out || n < 0 || a < 0 || m < 0 || a > n || m > n || n >= PROJ_LF) return SFS2D_E_ARG;
+  const double* lf = proj_lf_table();
+  const double c = proj_lnc(lf, (uint32_t)n, (uint32_t)a, (uint32_t)m);
+  for (int32_t j = 0; j <= m; ++j) w_out[j] = proj_w(lf, c, (uint32_t)n, (uint32_t)a, (uint32_t)m, (uint32_t)j);
+  return 0;
+}
+
+int sfs2d_plan_project(sfs2d_plan* pl, int32_t m1, int32_t m2, const int64_t* rec, const int32_t* grp, int64_t nsel,
+                       int64_t ngroups, int64_t* out_dev, int32_t* e_out) {
+  if (!pl) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  const sfs2d_data* d = pl->data;
+  if (pl->runs == 0)
+    return set_err(ctx, SFS2D_E_ARG, pl->base ? "project before the base plan's first run (an attached plan has no records yet)"
+                                              : "project before the plan's first run (no records yet)");
+  if (m1 < 2 || m1 > pl->K.n1 || m2 < 2 || m2 > pl->K.n2)
+    return set_err(ctx, SFS2D_E_ARG, "project: (m1, m2) = (" + std::to_string(m1) + ", " + std::to_string(m2) +
+                                         ") outside [2, " + std::to_string(pl->K.n1) + "] x [2, " + std::to_string(pl->K.n2) + "]");
+  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project: data set too large for 32-bit SNP indices");
+  if (nsel < 0) return set_err(ctx, SFS2D_E_ARG, "project: nsel must be >= 0");
+  if (ngroups < 1) return set_err(ctx, SFS2D_E_ARG, "project: ngroups must be >= 1");
+  if (!rec && nsel != pl->nrec)
+    return set_err(ctx, SFS2D_E_ARG, "project: rec == NULL selects every record in order: nsel must be the plan's record count");
+  if (rec && !grp) return set_err(ctx, SFS2D_E_ARG, "project: grp == NULL needs rec == NULL (group i = record i)");
+  if (nsel > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project: more than 2^32 - 1 selection entries");
+  if (!grp && nsel > ngroups)
+    return set_err(ctx, SFS2D_E_ARG, "project: group i = record i needs ngroups >= the plan's record count");
+  const int64_t roww = (int64_t)(m1 + 1) * (m2 + 1) + 2;   // at most 255 x 255 + 2 words
+  if (ngroups > 0xffffffffll || ngroups > (INT64_MAX / 8) / roww)
+    return set_err(ctx, SFS2D_E_NOMEM, "project: " + std::to_string(ngroups) + " rows of " + std::to_string(roww) +
+                                           " int64 words do not fit");
+  pl->proj_sel_h.clear();
+  pl->proj_sel_h.reserve((size_t)nsel);
+  // B: the SNPs one group can receive -- its entries times the bound on one entry's SNPs (a record's: plan_create's
+  // maxsnp; with chromosome entries in the selection, the longest chromosome, which is no smaller)
+  int64_t per_entry = std::max<int64_t>(1, pl->maxsnp);
+  for (int64_t i = 0; i < nsel; ++i) {
+    const int64_t r = rec ? rec[i] : i, g = grp ? (int64_t)grp[i] : i;
+    if (g < 0 || g >= ngroups)
+      return set_err(ctx, SFS2D_E_ARG, "project: entry " + std::to_string(i) + ": group " + std::to_string(g) +
+                                           " outside [0, " + std::to_string(ngroups) + ")");
+    if (r < 0) {   // -(c + 1): the whole chromosome c
+      const int64_t c = -(r + 1);
+      if (c >= d->nchrom)
+        return set_err(ctx, SFS2D_E_ARG, "project: entry " + std::to_string(i) + ": chromosome " + std::to_string(c) +
+                                             " outside [0, " + std::to_string(d->nchrom) + ")");
+      // (in pieces of PROJ_CHUNK SNPs, consecutive entries of one group: a chromosome is streamed by many
+      // workgroups, where a record's range is known on the device alone)
+      const int64_t cb = d->chrom_off[(size_t)c], ce = d->chrom_off[(size_t)c + 1];
+      for (int64_t s = cb; s < ce; s += PROJ_CHUNK)
+        pl->proj_sel_h.push_back(ProjSel{0xffffffffu, (uint32_t)g, (uint32_t)s, (uint32_t)std::min<int64_t>(s + PROJ_CHUNK, ce)});
+      per_entry = std::max<int64_t>(per_entry, ce - cb);
+    } else {
+      if (r >= pl->nrec)
+        return set_err(ctx, SFS2D_E_ARG, "project: entry " + std::to_string(i) + ": record " + std::to_string(r) +
+                                             " outside [0, " + std::to_string(pl->nrec) + ")");
+      pl->proj_sel_h.push_back(ProjSel{(uint32_t)r, (uint32_t)g, 0u, 0u});
+    }
+  }
+  int64_t maxent = nsel ? 1 : 0;   // the most entries of one group (grp == NULL: one each)
+  if (grp) {
+    std::vector<int32_t> gs(grp, grp + nsel);
+    std::sort(gs.begin(), gs.end());
+    for (int64_t i = 0, run = 0; i < nsel; ++i) {
+      run = (i && gs[(size_t)i] == gs[(size_t)i - 1]) ? run + 1 : 1;
+      maxent = std::max(maxent, run);
+    }
+  }
+  int e;
+  {
+    const unsigned __int128 B = (unsigned __int128)std::max<int64_t>(1, maxent) * (unsigned __int128)per_entry;
+    int b = 0;
+    while (b < 64 && (B >> b) != 0) ++b;   // bit length of B
+    e = std::min(40, 62 - b);
+    if (e < 8)
+      return set_err(ctx, SFS2D_E_CAP, "project: " + std::to_string(maxent) + " entries of up to " + std::to_string(per_entry) +
+                                           " SNPs in one group leave fewer than 8 fraction bits in 64-bit sums");
+  }
+  if (e_out) *e_out = e;
+  nsel = (int64_t)pl->proj_sel_h.size();   // (from here on: the entries the kernel walks)
+  if (nsel > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project: more than 2^32 - 1 selection entries");
+  const int64_t words = ngroups * roww;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = CTX_STREAM(ctx);
+  if (!ctx->d_lf) {
+    int rc = dalloc(ctx, &ctx->d_lf, (size_t)PROJ_LF);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(ctx->d_lf, proj_lf_table(), sizeof(double) * PROJ_LF, hipMemcpyHostToDevice));
+  }
+  if ((size_t)nsel > pl->proj_sel_cap || (!out_dev && (size_t)words > pl->proj_cap)) {
+    HIPCHK(ctx, hipStreamSynchronize(st));   // an earlier call may still read what is replaced
+    if ((size_t)nsel > pl->proj_sel_cap) {
+      hipFree(pl->d_proj_sel);
+      pl->proj_sel_cap = 0;
+      int rc = dalloc(ctx, &pl->d_proj_sel, (size_t)nsel);
+      if (rc) return rc;
+      pl->proj_sel_cap = (size_t)nsel;
+    }
+    if (!out_dev && (size_t)words > pl->proj_cap) {
+      hipFree(pl->d_proj);
+      pl->proj_cap = 0;
+      pl->proj_groups = -1;
+      int rc = dalloc(ctx, &pl->d_proj, (size_t)words);
+      if (rc) {
+        (void)hipGetLastError();
+        return rc;
+      }
+      pl->proj_cap = (size_t)words;
+    }
+  }
+  int64_t* out = out_dev ? out_dev : pl->d_proj;
+  // the row's u64 histogram in LDS while a CU can hold it beside the 4 KB table of ln k!; above the default limit
+  // the kernels opt in, and a refusal selects the global-atomic instantiations.  The projection changes from call to
+  // call and the limit belongs to the kernels, not to a plan: per device it only grows.
+  const size_t lds = sizeof(unsigned long long) * (size_t)roww;
+  bool ldsh = lds + 4096 <= 160 * 1024;
+  if (ldsh && lds > 64 * 1024) {
+    static std::mutex mu;
+    static std::map<int, size_t> granted;   // device -> the dynamic LDS its k_proj_win instantiations may take
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& have = granted[ctx->device];
+    if (lds > have) {
+      if (set_max_lds<ProjWin>(lds) != hipSuccess) {
+        (void)hipGetLastError();
+        ldsh = false;
+      } else {
+        have = lds;
+      }
+    }
+  }
+  HIPCHK(ctx, hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)words, st));
+  pl->proj_last = out;
+  pl->proj_groups = ngroups;
+  pl->proj_roww = roww;
+  pl->proj_e = e;
+  if (nsel == 0) return 0;
+  HIPCHK(ctx, hipMemcpyAsync(pl->d_proj_sel, pl->proj_sel_h.data(), sizeof(ProjSel) * (size_t)nsel, hipMemcpyHostToDevice, st));
+  int rc = 0;
+  const ProjWin::Fn k = variant(ctx, ProjWin{pl->cnt, ldsh}, "k_proj_win", &rc);
+  if (!k) return rc;
+  // A contiguous run of the selection per workgroup, as many workgroups as are resident with the row in LDS (one
+  // entry each at most).  Unlike k_spec_win the kernel is bound by its fp64 weights, not by the flushes: one
+  // chromosome entry at (40, 40) of 50 took 790 us from 256 workgroups of 4,096-SNP pieces.
+  const int per_cu = ldsh ? (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds + 4096))) : 8;
+  const dim3 g((unsigned)std::min<int64_t>(nsel, (int64_t)per_cu * ctx->ncu));
+  const sfs2d_window* recs = pl->last_out ? pl->last_out : pl->d_out;
+  hipLaunchKernelGGL(k, g, dim3(PROJ_BLOCK), ldsh ? lds : 0, st, pl->K, d->counts, scan_src(pl), recs, pl->d_proj_sel,
+                     ctx->d_lf, reinterpret_cast<unsigned long long*>(out), (uint32_t)nsel, (uint32_t)pl->nrec,
+                     (uint32_t)ngroups, (uint32_t)d->n, (uint32_t)m1, (uint32_t)m2, std::ldexp(1.0, e),
+                     1ull << (62 - e));
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int sfs2d_plan_project_read(sfs2d_plan* pl, double* out_host, int64_t* used, int64_t* dropped, int64_t cap_groups,
+                            int64_t* ngroups_out, int64_t* words_per_group) {
+  if (!pl || !ngroups_out || !words_per_group) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  if (pl->proj_groups < 0) return set_err(ctx, SFS2D_E_ARG, "sfs2d_plan_project_read before sfs2d_plan_project");
+  *ngroups_out = pl->proj_groups;
+  *words_per_group = pl->proj_roww - 2;
+  if (cap_groups < pl->proj_groups) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
+  if (!out_host || !used || !dropped) return SFS2D_E_ARG;
+  const size_t roww = (size_t)pl->proj_roww, ngrid = roww - 2, ng = (size_t)pl->proj_groups;
+  std::vector<int64_t> raw;
+  try {
+    raw.resize(ng * roww);
+  } catch (const std::bad_alloc&) {
+    return set_err(ctx, SFS2D_E_NOMEM, "project_read: host staging buffer");
+  }
+  HIPCHK(ctx, hipMemcpyAsync(raw.data(), pl->proj_last, sizeof(int64_t) * raw.size(), hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
+  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
+  const double inv = std::ldexp(1.0, -pl->proj_e);
+  for (size_t g = 0; g < ng; ++g) {
+    const int64_t* r = raw.data() + g * roww;
+    for (size_t k = 0; k < ngrid; ++k) out_host[g * ngrid + k] = (double)r[k] * inv;
+    used[g] = r[ngrid];
+    dropped[g] = r[ngrid + 1];
+  }
   return 0;
 }
 

@@ -36,6 +36,12 @@ def spec_row_words(n1p: int, n2p: int) -> int:
     pop-2 folded, n2p + 1] (sfs2d_plan_spectra)."""
     return (2 * n1p + 1) * (2 * n2p + 1) + n1p + n2p + 2
 
+
+def proj_row_words(m1: int, m2: int) -> int:
+    """SFS2D_PROJ_ROW_WORDS: one group of projected window spectra as an int64 row [(m1 + 1) x (m2 + 1) grid, fixed
+    point | n_used | n_dropped] (sfs2d_plan_project)."""
+    return (m1 + 1) * (m2 + 1) + 2
+
 # the exported symbols of include/sfs2d.h (checked by tests/test_lib_abi.py)
 EXPORTS = [
     "sfs2d_abi_version", "sfs2d_ctx_create", "sfs2d_ctx_destroy", "sfs2d_last_error", "sfs2d_ctx_set_stream",
@@ -54,6 +60,7 @@ EXPORTS = [
     "sfs2d_plan_diversity", "sfs2d_plan_diversity_read",
     "sfs2d_plan_create_regions", "sfs2d_plan_attach_regions",
     "sfs2d_plan_spectra", "sfs2d_plan_spectra_read",
+    "sfs2d_plan_project", "sfs2d_plan_project_read", "sfs2d_project_weights",
 ]
 ABI_VERSION = 2   # SFS2D_ABI_VERSION of include/sfs2d.h
 
@@ -177,6 +184,9 @@ def lib():
     L.sfs2d_plan_diversity_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sfs2d_plan_spectra.argtypes = [vp, vp, vp, i64, i64, vp]
     L.sfs2d_plan_spectra_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.sfs2d_plan_project.argtypes = [vp, i32, i32, vp, vp, i64, i64, vp, C.POINTER(i32)]
+    L.sfs2d_plan_project_read.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.sfs2d_project_weights.argtypes = [i32, i32, i32, vp]
     L.sfs2d_data_synth_sims.argtypes = [vp, C.POINTER(SynthParams), vp, vp, i32, vp, i32, C.POINTER(vp)]
     L.sfs2d_data_read.argtypes = [vp, vp, vp, i64]
     L.sfs2d_ctx_use_own_stream.argtypes = [vp]

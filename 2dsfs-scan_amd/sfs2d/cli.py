@@ -45,6 +45,14 @@ chosen from the statistics with the clean None rules of the sliding scans.  ``--
 ``--regions``) writes ``<prefix>_regions_spectra.npz``: ``name``, ``sfs2d[nregions, n1 + 1, n2 + 1]``,
 ``sfs1d_pop1``, ``sfs1d_pop2`` in the BED file's order -- a spectrum per gene to hand to dadi / moments /
 fastsimcoal.
+
+``--project M1,M2`` (with ``--outlier-spectra`` or ``--region-spectra``; 2 <= M_k <= 2 pop_size_k) projects those
+spectra down hypergeometrically to M1 / M2 haploid samples on the GPU, as dadi's
+``projections=`` and easySFS do: only SNPs called in at least M_k alleles of both populations count, each spread
+over the bins its subsamples fall in.  The file stems gain ``_proj<M1>x<M2>``, the grids are floats of
+``(M1 + 1) x (M2 + 1)`` bins (foreground and background alike, folded unless ``--no-fold``; a tie of the joint fold
+stays where it is, dadi averages ties), the npz gains ``n_used`` and ``n_dropped`` and its 1D spectra are the grid's
+marginals; each output prints the share of its SNPs that the projection dropped.
 """
 from __future__ import annotations
 
@@ -148,6 +156,22 @@ def parse_outlier_spec(text):
     return key, q
 
 
+def parse_project(text, n1p: int, n2p: int):
+    """``M1,M2`` -> (M1, M2); ValueError with the reason for a malformed or out-of-range one."""
+    try:
+        m1, m2 = (int(x) for x in str(text).split(","))
+    except ValueError:
+        raise ValueError(f"--project {text!r}: expected M1,M2 (two integers)") from None
+    if not (2 <= m1 <= 2 * n1p and 2 <= m2 <= 2 * n2p):
+        raise ValueError(f"--project {text!r}: need 2 <= M1 <= {2 * n1p} and 2 <= M2 <= {2 * n2p}")
+    return m1, m2
+
+
+def _dropped_share(used, dropped) -> str:
+    n = int(used) + int(dropped)
+    return f"{int(dropped)} of {n} SNPs dropped ({100.0 * int(dropped) / n:.2f} %)" if n else "no SNPs"
+
+
 def _fmt_pct(q: float) -> str:
     return f"{round((1.0 - q) * 100.0, 6):g}"
 
@@ -199,6 +223,9 @@ def main(argv=None):
                          "their per-bin residuals -> <prefix>_<size>_<KEY>_top<pct>{.fs,_background.fs,_residuals.csv}")
     ap.add_argument("--region-spectra", action="store_true",
                     help="with --regions: every region's 2D and folded 1D spectra -> <prefix>_regions_spectra.npz")
+    ap.add_argument("--project", default=None, metavar="M1,M2",
+                    help="with --outlier-spectra / --region-spectra: project the spectra down to M1 / M2 haploid "
+                         "samples (SNPs with fewer called alleles are dropped); stems gain _proj<M1>x<M2>")
     ap.add_argument("--out-prefix", default="stats")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="VCF parser threads (0 = all)")
@@ -217,6 +244,15 @@ def main(argv=None):
             ap.error("--outlier-spectra FST:Q needs --fst")
     if a.region_spectra and a.regions is None:
         ap.error("--region-spectra needs --regions")
+    pkw, ptag = {}, ""   # (without the flag every call below is the one it was)
+    if a.project is not None:
+        if not ospecs and not a.region_spectra:
+            ap.error("--project applies to --outlier-spectra / --region-spectra: give one of them")
+        try:
+            pkw = dict(project=parse_project(a.project, a.pop1_size, a.pop2_size))
+        except ValueError as e:
+            ap.error(str(e))
+        ptag = "_proj{}x{}".format(*pkw["project"])
     null = a.null_replicates is not None
     block = None
     if a.null_block is not None:
@@ -274,24 +310,31 @@ def main(argv=None):
     def spectra_out(size, **geometry):
         # (the new flags alone: a scan of its own per file, nothing of the calls above changes)
         for key, q in ospecs:
-            res = obj.outlier_spectra(packed, key=SPECTRA_KEYS[key], q=q, fst=key == "FST", **geometry)
-            stem = f"{a.out_prefix}_{size}_{key}_top{_fmt_pct(q)}"
+            res = obj.outlier_spectra(packed, key=SPECTRA_KEYS[key], q=q, fst=key == "FST", **geometry, **pkw)
+            stem = f"{a.out_prefix}_{size}_{key}_top{_fmt_pct(q)}{ptag}"
             outs.extend(write_outlier_spectra(stem, res, not a.no_fold, (a.pop1, a.pop2)))
             print(f"outlier_spectra {size} {key} >= q{q:g}: {len(res['labels'])} windows, pooled T2D {res['T2D']} -> "
                   f"{stem}.fs", file=sys.stderr)
+            if pkw:
+                print(f"projection {pkw['project']}: foreground {_dropped_share(res['n_used'], res['n_dropped'])}, "
+                      f"background {_dropped_share(res['background_n_used'], res['background_n_dropped'])}", file=sys.stderr)
 
     def region_spectra_out():
         if not a.region_spectra:
             return
         import numpy as np
-        sp = obj.window_spectra(packed, regions=rg)
+        sp = obj.window_spectra(packed, regions=rg, **pkw)
         keys = rg.keys()
-        path = f"{a.out_prefix}_regions_spectra.npz"
+        path = f"{a.out_prefix}_regions_spectra{ptag}.npz"
+        extra = {k: np.array([sp[r][k] for r in keys], np.int64) for k in (("n_used", "n_dropped") if pkw else ())}
         np.savez(path, name=np.array(keys, dtype=str), sfs2d=np.stack([sp[k]["sfs2d"] for k in keys]),
                  sfs1d_pop1=np.stack([sp[k]["sfs1d_pop1"] for k in keys]),
-                 sfs1d_pop2=np.stack([sp[k]["sfs1d_pop2"] for k in keys]))
+                 sfs1d_pop2=np.stack([sp[k]["sfs1d_pop2"] for k in keys]), **extra)
         outs.append(path)
         print(f"window_spectra: {len(keys)} regions -> {path}", file=sys.stderr)
+        if pkw:
+            print(f"projection {pkw['project']}: {_dropped_share(extra['n_used'].sum(), extra['n_dropped'].sum())}",
+                  file=sys.stderr)
     t = time.perf_counter()
     if a.step is not None:   # sliding windows: every size from one upload and one k_prep pass
         if null:

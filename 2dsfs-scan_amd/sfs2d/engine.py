@@ -396,6 +396,40 @@ class Plan:
         self.eng.check(self.eng.lib.sfs2d_plan_spectra_read(self.h, L.ptr(out), out.size, C.byref(n)))
         return out
 
+    def project(self, m1: int, m2: int, rec=None, grp=None, ngroups: Optional[int] = None,
+                out_dev_ptr: Optional[int] = None):
+        """The joint spectra of chosen records of this plan's last run, projected down hypergeometrically to the
+        haploid sample sizes ``(m1, m2)`` and summed into groups (sfs2d_plan_project): ``(float64[ngroups, m1 + 1,
+        m2 + 1], used, dropped)`` -- the unfolded grids of raw alt counts (sfs2d.spectra.fold_projected /
+        projected_marginals do the linear rest) and, per group, the member SNPs used (called counts >= m in both
+        populations) and dropped.  ``rec`` / ``grp`` / ``ngroups`` as ``spectra``; in addition ``rec[i] = -(c + 1)``
+        names the whole chromosome c.  The grids are multiples of ``2 ** -self.project_e``, the fixed point the
+        call chose; two calls give equal arrays.  With ``out_dev_ptr`` (a device buffer of ngroups rows of
+        ``L.proj_row_words(m1, m2)`` int64) nothing is copied to the host and None is returned."""
+        m1, m2 = int(m1), int(m2)
+        r = None if rec is None else np.ascontiguousarray(np.asarray(rec, np.int64).reshape(-1))
+        g = None if grp is None else np.ascontiguousarray(np.asarray(grp, np.int32).reshape(-1))
+        if r is not None and g is not None and len(r) != len(g):
+            raise ValueError("project: rec and grp differ in length")
+        nsel = len(r) if r is not None else (len(g) if g is not None else self.nrec)
+        if ngroups is None:
+            ngroups = max(1, self.nrec if g is None else (int(g.max()) + 1 if len(g) else 1))
+        ngroups = int(ngroups)
+        rp = None if r is None else C.c_void_p(r.ctypes.data)
+        gp = None if g is None else C.c_void_p(g.ctypes.data)
+        e = C.c_int32()
+        self.eng.check(self.eng.lib.sfs2d_plan_project(self.h, m1, m2, rp, gp, nsel, ngroups,
+                                                       C.c_void_p(out_dev_ptr) if out_dev_ptr else None, C.byref(e)))
+        self.project_e = e.value
+        if out_dev_ptr:
+            return None
+        out = np.zeros((ngroups, m1 + 1, m2 + 1), np.float64)
+        used, dropped = np.zeros(ngroups, np.int64), np.zeros(ngroups, np.int64)
+        n, w = C.c_int64(), C.c_int64()
+        self.eng.check(self.eng.lib.sfs2d_plan_project_read(self.h, L.ptr(out), L.ptr(used), L.ptr(dropped), ngroups,
+                                                            C.byref(n), C.byref(w)))
+        return out, used, dropped
+
     def bg_buffer(self):
         p = C.c_void_p()
         nb = C.c_int64()

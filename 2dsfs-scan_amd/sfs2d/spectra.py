@@ -16,10 +16,23 @@ Per record with SNP range [begin, end), under the plan's position filter, varian
 
 A group is the SUM over its selection entries.  On overlapping windows (sliding windows, regions) that is a sum
 over windows, not the spectrum of their union: a SNP inside two selected windows is counted twice.
+
+Projected spectra (k_proj_win, csrc/sfs2d_proj.hpp; ``Plan.project``): the grid above bins a
+SNP by its raw alt count whatever its called count, which a model fit (dadi, moments, fastsimcoal) cannot take
+when calls are missing.  For a projection ``(m1, m2)`` of haploid sample sizes a member SNP (one the plan's run
+counts in its 2D SFS) with called counts n_k = r_k + a_k >= m_k in both populations is *used* and adds
+``h(j1; n1, a1, m1) h(j2; n2, a2, m2)``, ``h(j; n, a, m) = C(a, j) C(n - a, m - j) / C(n, m)``, to bin (j1, j2) of a
+dense (m1 + 1) x (m2 + 1) grid; any other member is *dropped*.  The device returns the UNFOLDED grid of raw alt
+counts; what is linear is done here: the joint fold (``fold_projected``: bin (j1, j2) with 2 (j1 + j2) > m1 + m2 is
+added to (m1 - j1, m2 - j2); a tie stays where it is, as the scan's fold leaves it -- dadi's ``fold()`` AVERAGES
+the two halves of a tie instead), the two 1D marginals (``projected_marginals``) and their folds
+(``fold1d_projected``).  ``project_np`` is the exact twin (rational weights), the definition the tests compare
+against.
 """
 from __future__ import annotations
 
 import math
+from fractions import Fraction
 
 import numpy as np
 
@@ -27,7 +40,8 @@ from . import _lib as L
 from .diversity import _filter_mask
 
 __all__ = ["split_row", "window_spectra_np", "select_top", "residuals", "pooled_t2d", "write_dadi_fs",
-           "read_dadi_fs", "RESIDUAL_COLUMNS"]
+           "read_dadi_fs", "RESIDUAL_COLUMNS", "project_weights_exact", "project_np", "fold_projected",
+           "projected_marginals", "fold1d_projected"]
 
 RESIDUAL_COLUMNS = ["x1", "x2", "fg_count", "bg_count", "fg_p", "bg_p", "diff", "t2d_term"]
 
@@ -101,6 +115,145 @@ def window_spectra_np(p, recs, cfg, rec=None, grp=None, ngroups=None) -> np.ndar
     return out
 
 
+def project_weights_exact(n: int, a: int, m: int):
+    """The hypergeometric weights h(j; n, a, m) = C(a, j) C(n - a, m - j) / C(n, m), j = 0 .. m, as exact
+    Fractions (0 outside the support max(0, m - (n - a)) <= j <= min(m, a))."""
+    n, a, m = int(n), int(a), int(m)
+    if not (0 <= a <= n and 0 <= m <= n):
+        raise ValueError(f"project_weights_exact: need 0 <= a <= n and 0 <= m <= n, got n={n} a={a} m={m}")
+    den = math.comb(n, m)
+    return [Fraction(math.comb(a, j) * math.comb(n - a, m - j), den) for j in range(m + 1)]
+
+
+def _members(p, lo, hi, cfg, n1p, n2p, fold):
+    """(r1, a1, r2, a2) int64 of the SNPs of [lo, hi) that the plan's run counts in its 2D SFS."""
+    m = _filter_mask(p, lo, hi, cfg)
+    c = p.counts[lo:hi][m]
+    r1, a1, r2, a2 = [((c >> np.uint32(s)) & np.uint32(0xFF)).astype(np.int64) for s in (0, 8, 16, 24)]
+    x1, x2 = a1, a2
+    if fold:
+        sw = (a1 + a2) > (n1p + n2p)
+        x1, x2 = np.where(sw, r1, a1), np.where(sw, r2, a2)
+    keep = (x1 != 0) | (x2 != 0)
+    return r1[keep], a1[keep], r2[keep], a2[keep]
+
+
+def _project_range(p, lo, hi, cfg, n1p, n2p, fold, m1, m2, D1, D2):
+    """(grid of integers as an object array: the exact grid times D1 D2, n_used, n_dropped) of the SNP range
+    [lo, hi).  D_k: a common multiple of C(n, m_k) over the called counts n >= m_k of the data set, so that every
+    weight is an integer over D_k."""
+    grid = np.zeros((m1 + 1, m2 + 1), object)
+    if hi <= lo:
+        return grid, 0, 0
+    r1, a1, r2, a2 = _members(p, lo, hi, cfg, n1p, n2p, fold)
+    used = (r1 + a1 >= m1) & (r2 + a2 >= m2)
+
+    def weights(r, a, m, D):   # D h(j; r + a, a, m) over the support, as integers
+        lo_j, hi_j = max(0, m - r), min(m, a)
+        s = D // math.comb(r + a, m)
+        return lo_j, np.array([math.comb(a, j) * math.comb(r, m - j) * s for j in range(lo_j, hi_j + 1)], object)
+    # SNPs with equal counts add equal terms, and the sum factorises: per distinct (r1, a1) the outer product of
+    # its pop-1 weights with the sum of the pop-2 weight vectors of its SNPs (each distinct (r2, a2) times its count)
+    keys, cnt = np.unique(np.stack([r1[used], a1[used], r2[used], a2[used]], axis=1), axis=0, return_counts=True)
+    by1, w2 = {}, {}
+    for (q1, b1, q2, b2), k in zip(keys.tolist(), cnt.tolist()):
+        if (q2, b2) not in w2:
+            w2[(q2, b2)] = weights(q2, b2, m2, D2)
+        l2, v2 = w2[(q2, b2)]
+        v = by1.setdefault((q1, b1), np.zeros(m2 + 1, object))
+        v[l2:l2 + len(v2)] += k * v2
+    for (q1, b1), v in by1.items():
+        l1, v1 = weights(q1, b1, m1, D1)
+        nz = np.nonzero(v)[0]
+        grid[l1:l1 + len(v1), nz[0]:nz[-1] + 1] += np.multiply.outer(v1, v[nz[0]:nz[-1] + 1])
+    return grid, int(used.sum()), int((~used).sum())
+
+
+def project_np(p, recs, cfg, m1: int, m2: int, rec=None, grp=None, ngroups=None, exact: bool = False):
+    """The twin of ``Plan.project``, with exact weights: ``(float64[ngroups, m1 + 1, m2 + 1], used, dropped)`` from
+    the packed SNPs ``p``, the plan's window records ``recs`` and its configuration ``cfg`` (as
+    ``window_spectra_np`` takes them; ``cfg.fold`` decides membership alone -- the grid is unfolded).  Every weight
+    is a ratio of ``math.comb`` values; the bins are summed as integers over one common denominator and divided
+    once, correctly rounded.  ``rec[i] = -(c + 1)`` names the whole chromosome c.  ``exact``: return the grids as
+    object arrays of Fractions."""
+    n1p, n2p, fold = int(cfg.n1p), int(cfg.n2p), bool(cfg.fold)
+    m1, m2 = int(m1), int(m2)
+    if not (2 <= m1 <= 2 * n1p and 2 <= m2 <= 2 * n2p):
+        raise ValueError(f"project: (m1, m2) = ({m1}, {m2}) outside [2, {2 * n1p}] x [2, {2 * n2p}]")
+    nrec = len(recs)
+    rec = np.arange(nrec, dtype=np.int64) if rec is None else np.asarray(rec, np.int64).reshape(-1)
+    grp = np.arange(len(rec), dtype=np.int64) if grp is None else np.asarray(grp, np.int64).reshape(-1)
+    if len(rec) != len(grp):
+        raise ValueError("rec and grp differ in length")
+    if ngroups is None:
+        ngroups = max(1, int(grp.max()) + 1 if len(grp) else 1)
+    ngroups = int(ngroups)
+    c = p.counts
+    nc1 = ((c & np.uint32(0xFF)) + ((c >> np.uint32(8)) & np.uint32(0xFF))).astype(np.int64)
+    nc2 = (((c >> np.uint32(16)) & np.uint32(0xFF)) + (c >> np.uint32(24))).astype(np.int64)
+    D1 = math.lcm(*[math.comb(n, m1) for n in np.unique(nc1[nc1 >= m1]).tolist()])
+    D2 = math.lcm(*[math.comb(n, m2) for n in np.unique(nc2[nc2 >= m2]).tolist()])
+    grids = np.zeros((ngroups, m1 + 1, m2 + 1), object)
+    used, dropped = np.zeros(ngroups, np.int64), np.zeros(ngroups, np.int64)
+    cache = {}
+    for s, g in zip(rec.tolist(), grp.tolist()):
+        if not -p.nchrom <= s < nrec or not 0 <= g < ngroups:
+            raise ValueError(f"entry (record {s}, group {g}) out of range")
+        if s < 0:
+            lo, hi = int(p.chrom_off[-s - 1]), int(p.chrom_off[-s])
+        else:
+            r = recs[s]
+            if int(r["flags"]) & (L.W_EMPTY | L.W_EXTRA):
+                continue
+            hi = min(int(r["end"]), p.n)
+            lo = min(int(r["begin"]), hi)
+        if (lo, hi) not in cache:
+            cache[(lo, hi)] = _project_range(p, lo, hi, cfg, n1p, n2p, fold, m1, m2, D1, D2)
+        gr, u, d = cache[(lo, hi)]
+        grids[g] += gr
+        used[g] += u
+        dropped[g] += d
+    D = D1 * D2
+    flat = grids.ravel().tolist()
+    if exact:
+        out = np.empty(len(flat), object)
+        out[:] = [Fraction(x, D) for x in flat]
+        return out.reshape(grids.shape), used, dropped
+    # (int / int: one correctly rounded division per bin)
+    return np.array([x / D for x in flat], np.float64).reshape(grids.shape), used, dropped
+
+
+def fold_projected(grid):
+    """The joint fold of an unfolded projected grid (..., m1 + 1, m2 + 1): bin (j1, j2) with 2 (j1 + j2) > m1 + m2
+    is added to (m1 - j1, m2 - j2) and zeroed; a tie, 2 (j1 + j2) == m1 + m2, stays where it is, as the scan's fold
+    leaves a tied SNP (dadi's ``Spectrum.fold`` averages the two halves of a tie instead).  Linear: integer grids
+    stay integer, object (Fraction) grids exact."""
+    g = np.array(grid, copy=True)
+    m1, m2 = g.shape[-2] - 1, g.shape[-1] - 1
+    i, j = np.indices((m1 + 1, m2 + 1))
+    hi = 2 * (i + j) > m1 + m2
+    zero = 0 if g.dtype == object else g.dtype.type(0)
+    return np.where(hi, zero, g) + np.where(hi, g, zero)[..., ::-1, ::-1]
+
+
+def projected_marginals(grid):
+    """The two 1D marginals (..., m1 + 1) and (..., m2 + 1) of an unfolded projected grid: the 1D projections of
+    the used SNPs' raw alt counts to m1 and to m2 (a SNP's weights over the other population sum to 1)."""
+    g = np.asarray(grid)
+    return g.sum(axis=-1), g.sum(axis=-2)
+
+
+def fold1d_projected(sfs1d):
+    """The fold ``min(j, m - j)`` of an unfolded 1D projected spectrum (..., m + 1): entry j of the result, j <=
+    m // 2, is ``x[j] + x[m - j]`` (``x[j]`` alone where j == m - j), the entries above m // 2 are 0."""
+    x = np.asarray(sfs1d)
+    m = x.shape[-1] - 1
+    out = np.zeros_like(x)
+    for j in range(m // 2 + 1):
+        out[..., j] = x[..., j] if j == m - j else x[..., j] + x[..., m - j]
+    return out
+
+
 def select_top(rows: dict, key: str, q: float):
     """The labels of the rows of a scan's result dict whose ``key`` lies in the top 1 - q of its values, in scan
     order: candidates are the rows whose value is neither None nor NaN (+inf is kept: such a window is the most
@@ -171,7 +324,8 @@ def residual_rows(res: dict):
     fg, bg = res["fg_count"], res["bg_count"]
     out = []
     for i, j in zip(*np.nonzero((fg != 0) | (bg != 0))):
-        out.append([int(i), int(j), int(fg[i, j]), bg[i, j].item(), float(res["fg_p"][i, j]), float(res["bg_p"][i, j]),
+        f = fg[i, j].item()   # (an integer grid's count as int, as before; a projected grid's as the float it is)
+        out.append([int(i), int(j), f if isinstance(f, float) else int(f), bg[i, j].item(), float(res["fg_p"][i, j]), float(res["bg_p"][i, j]),
                     float(res["diff"][i, j]), float(res["t2d_term"][i, j])])
     return out
 

@@ -807,8 +807,26 @@ class LikelihoodInference_jointSFS:
         cfg = self._cfg(p, window_mode=L.WINDOW_BP if bp else L.WINDOW_SNPS, window=w, step=step, **kw)
         return cfg, "bp" if bp else "snps", w, step, None
 
+    def _check_project(self, project):
+        """(m1, m2) of a ``project=`` argument, ValueError when it is no pair within [2, 2 pop_size]."""
+        try:
+            m1, m2 = (int(x) for x in project)
+        except (TypeError, ValueError):
+            raise ValueError(f"project: a pair (m1, m2) of haploid sample sizes, got {project!r}") from None
+        if not (2 <= m1 <= 2 * self.pop1_size and 2 <= m2 <= 2 * self.pop2_size):
+            raise ValueError(f"project: ({m1}, {m2}) outside [2, {2 * self.pop1_size}] x [2, {2 * self.pop2_size}]")
+        return m1, m2
+
+    def _projected_entry(self, grid, used, dropped):
+        """One projected group as the spectra methods return it: folded when the object folds."""
+        from sfs2d import spectra as SP
+        s1, s2 = SP.projected_marginals(grid)
+        if self.fold:
+            grid, s1, s2 = SP.fold_projected(grid), SP.fold1d_projected(s1), SP.fold1d_projected(s2)
+        return {"sfs2d": grid, "sfs1d_pop1": s1, "sfs1d_pop2": s2, "n_used": int(used), "n_dropped": int(dropped)}
+
     def window_spectra(self, data_dict, window_size=None, snp_window_size=None, step_size=None, regions=None,
-                       select=None):
+                       select=None, project=None):
         """The spectra themselves of a scan's windows, where the scans return them reduced to T2D / T1D:
         {label: {"sfs2d": int64 grid (2 pop1_size + 1, 2 pop2_size + 1), "sfs1d_pop1", "sfs1d_pop2": folded 1D
         spectra}}, labels as combined_scan (``window_size``; sliding_scan with ``step_size``), scan_perChr_bySNPs
@@ -817,8 +835,16 @@ class LikelihoodInference_jointSFS:
         calculate_2d_sfs over the window under the object's filters and fold -- bin (0, 0) is 0, the last bin is
         counted; the 1D spectra hold the inner bins 1 .. pop_size - 1 that T1D reads, entries 0 and pop_size are 0.
         Summed on the GPU from the data the scan holds (k_spec_win).  The
-        reference cuts the windows' SNPs into new VCFs and reads them again (sims_scan.py:726-936)."""
+        reference cuts the windows' SNPs into new VCFs and reads them again (sims_scan.py:726-936).
+        ``project`` = (m1, m2): the spectra projected down hypergeometrically to m1 / m2 haploid samples
+        (k_proj_win), what a model fit takes when calls are missing: "sfs2d" is then a
+        float64 (m1 + 1, m2 + 1) grid of the SNPs called in at least m_k alleles of both populations, "sfs1d_pop1" /
+        "sfs1d_pop2" its two marginals (m_k + 1 entries, every bin), all three folded when the object folds (a tie
+        of the joint fold stays where it is; dadi averages ties), and "n_used" / "n_dropped" count the window's SNPs
+        that reached the sample sizes and those that did not."""
         self._no_distributed_spectra("window_spectra")
+        if project is not None:
+            project = self._check_project(project)
         p = self._pack(data_dict)
         cfg, kind, w, step, rg = self._spectra_cfg(p, window_size, snp_window_size, step_size, regions,
                                                    bg_mode=L.BG_PER_CHROM)
@@ -839,12 +865,18 @@ class LikelihoodInference_jointSFS:
                 for lb in labels:
                     if lb not in index:
                         raise ValueError(f"window_spectra: no window labelled {lb!r}")
-                rows = pl.spectra([index[lb] for lb in labels], np.arange(len(labels), dtype=np.int32),
-                                  max(1, len(labels)))
+                if project is not None:
+                    proj = pl.project(*project, [index[lb] for lb in labels], np.arange(len(labels), dtype=np.int32),
+                                      max(1, len(labels)))
+                else:
+                    rows = pl.spectra([index[lb] for lb in labels], np.arange(len(labels), dtype=np.int32),
+                                      max(1, len(labels)))
             finally:
                 pl.close()
         finally:
             dev.close()
+        if project is not None:
+            return {lb: self._projected_entry(g, u, d) for lb, g, u, d in zip(labels, *proj)}
         out = {}
         for lb, row in zip(labels, rows):
             g, f1, f2 = SP.split_row(row, self.pop1_size, self.pop2_size)
@@ -870,7 +902,7 @@ class LikelihoodInference_jointSFS:
         return rows
 
     def outlier_spectra(self, data_dict, window_size=None, key="T2D", q=0.99, fst=False, snp_window_size=None,
-                        step_size=None, background_chromosome=None):
+                        step_size=None, background_chromosome=None, project=None):
         """The joint spectrum of a scan's outlier windows beside its background, and which bins drive T2D: the
         windows whose ``key`` (T2D, T1D_pop1, T1D_pop2, new_term_pop1, new_term_pop2, T2D_diff, snp_count; or FST
         with ``fst``) is in the top 1 - ``q`` of the scan (sfs2d.spectra.select_top: value >= the ``q`` quantile
@@ -885,8 +917,15 @@ class LikelihoodInference_jointSFS:
         background (the sum of the residual terms; None when either is empty)}.  On sliding windows the pool is a
         sum over windows, not the spectrum of their union: a SNP in two selected windows is counted twice.  The
         reference merges the outlier windows' VCFs with an outside tool, reads them again and subtracts the
-        normalised spectra (sims_scan.py:726-936)."""
+        normalised spectra (sims_scan.py:726-936).
+        ``project`` = (m1, m2): the pooled foreground and the background both projected down to m1 / m2 haploid
+        samples on the GPU (``window_spectra``'s ``project``; the background through whole-chromosome entries of the
+        same call, under the scan's own membership), float64 grids folded when the object folds; the residuals
+        and the pooled T2D come from them.  Added keys: "n_used" / "n_dropped" of the foreground,
+        "background_n_used" / "background_n_dropped"."""
         self._no_distributed_spectra("outlier_spectra")
+        if project is not None:
+            project = self._check_project(project)
         if key == "FST" and not fst:
             raise ValueError("key 'FST' needs fst=True")
         p = self._pack(data_dict)
@@ -913,17 +952,29 @@ class LikelihoodInference_jointSFS:
                 top = SP.select_top(rows, key, q)
                 index = {lb: i for i, lb in enumerate(labels) if lb is not None}
                 sel = [index[lb] for lb in top]
-                row = pl.spectra(sel, np.zeros(len(sel), np.int32), 1)[0]
-                if bg is not None:
-                    bg_grid, bg_names = np.asarray(bg[0], np.int64), [background_chromosome]
-                else:
-                    chroms = sorted(set(int(recs[i]["chrom"]) for i in sel))
+                chroms = ([p.chrom_names.index(background_chromosome)] if bg is not None
+                          else sorted(set(int(recs[i]["chrom"]) for i in sel)))
+                if project is not None:   # group 0: the pooled windows; group 1: the chromosomes, whole
+                    proj = pl.project(*project, sel + [-(c + 1) for c in chroms], [0] * len(sel) + [1] * len(chroms), 2)
                     bg_names = [p.chrom_names[c] for c in chroms]
-                    bg_grid = sum(np.asarray(eng.bg_hist(dev, cfg, c)[0], np.int64) for c in chroms)
+                else:
+                    row = pl.spectra(sel, np.zeros(len(sel), np.int32), 1)[0]
+                    if bg is not None:
+                        bg_grid, bg_names = np.asarray(bg[0], np.int64), [background_chromosome]
+                    else:
+                        bg_names = [p.chrom_names[c] for c in chroms]
+                        bg_grid = sum(np.asarray(eng.bg_hist(dev, cfg, c)[0], np.int64) for c in chroms)
             finally:
                 pl.close()
         finally:
             dev.close()
+        if project is not None:
+            f, b = (self._projected_entry(g, u, d) for g, u, d in zip(*proj))
+            res = SP.residuals(f["sfs2d"], b["sfs2d"])
+            return {"labels": top, "foreground": f["sfs2d"], "sfs1d_pop1": f["sfs1d_pop1"], "sfs1d_pop2": f["sfs1d_pop2"],
+                    "background": b["sfs2d"], "background_chromosomes": bg_names, "residuals": res,
+                    "T2D": SP.pooled_t2d(res), "n_used": f["n_used"], "n_dropped": f["n_dropped"],
+                    "background_n_used": b["n_used"], "background_n_dropped": b["n_dropped"]}
         g, f1, f2 = SP.split_row(row, self.pop1_size, self.pop2_size)
         res = SP.residuals(g, bg_grid)
         return {"labels": top, "foreground": g.copy(), "sfs1d_pop1": f1.copy(), "sfs1d_pop2": f2.copy(),

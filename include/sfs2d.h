@@ -41,7 +41,8 @@ extern "C" {
  * (additive); sfs2d_plan_null_run_blocks added (additive: sfs2d_null_params keeps its layout, the block length is
  * an argument); sfs2d_plan_diversity / _diversity_read and sfs2d_diversity added (additive);
  * sfs2d_plan_create_regions / sfs2d_plan_attach_regions added (additive: the intervals are arguments);
- * sfs2d_plan_spectra / _spectra_read added (additive) */
+ * sfs2d_plan_spectra / _spectra_read added (additive); sfs2d_plan_project / _project_read and
+ * sfs2d_project_weights added (additive) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -403,6 +404,46 @@ int sfs2d_plan_spectra(sfs2d_plan* plan, const int64_t* rec, const int32_t* grp,
 /* copy the last sfs2d_plan_spectra call's rows to host (synchronises); *nwords_out: ngroups x row words;
  * SFS2D_E_CAP: cap_words below it; SFS2D_E_ARG: no spectra call since the plan was created */
 int sfs2d_plan_spectra_read(sfs2d_plan* plan, int64_t* out_host, int64_t cap_words, int64_t* nwords_out);
+/* Projected window spectra: the joint spectrum of chosen records of the plan's last run,
+ * projected down hypergeometrically to the haploid sample sizes (m1, m2), 2 <= m_k <= 2 pop_size_k, and summed into
+ * groups -- what a model fit (dadi, moments, fastsimcoal) takes when calls are missing: sfs2d_plan_spectra bins a
+ * SNP by its raw alt count whatever its called count.  For a record with SNP range [begin, end) (clamped to the data
+ * set's SNP count):
+ *   member   a SNP that the plan's run counts in its 2D SFS (the position and variant_type filters, no (0, 0) SNPs)
+ *   used     a member with called counts n1 = r1 + a1 >= m1 and n2 = r2 + a2 >= m2 (surplus calls, n_k > 2 pop_size_k,
+ *            included); any other member is dropped
+ *   grid     a used SNP adds h(j1; n1, a1, m1) h(j2; n2, a2, m2) to bin (j1, j2) of the dense (m1 + 1) x (m2 + 1)
+ *            grid, row-major, with h(j; n, a, m) = C(a, j) C(n - a, m - j) / C(n, m) on its support
+ *            max(0, m - (n - a)) <= j <= min(m, a).  The RAW alt counts are projected; nothing is folded (the fold,
+ *            the marginals and their folds are linear: sfs2d/spectra.py forms them on the host).
+ * A group's row is SFS2D_PROJ_ROW_WORDS int64, laid out [grid, fixed point 2^-e | n_used | n_dropped], summed over
+ * the group's selection entries by sfs2d_plan_spectra's rules (a record listed twice counts twice, EMPTY and EXTRA
+ * records add nothing, a group without entries is all 0, overlapping windows are summed, not united).  Each term is
+ * rounded to nearest at 2^-e once and the sums are integer: two calls give byte-equal rows.  e is chosen per call,
+ * e = min(40, 62 - bitlen(B)), B = the largest number of entries of one group x the bound on an entry's SNPs (the
+ * plan's bound on a window's SNPs; the longest named chromosome if that is more), and reported in *e_out (NULL:
+ * not wanted).
+ * rec / grp / nsel / ngroups / out_dev: as sfs2d_plan_spectra, NULL forms included, and in addition rec[i] = -(c + 1)
+ * names the whole chromosome c of the plan's data set, [chrom_off[c], chrom_off[c + 1]), under the same membership:
+ * a projected per-chromosome background on any plan kind.  Enqueued on the ctx stream after the plan's last run;
+ * reads the records, the counts and (filtered plans) the per-SNP bins, writes out_dev alone: a following run, null
+ * run, diversity or spectra call finds everything as it was.
+ * SFS2D_E_ARG, the reason in sfs2d_last_error: a plan that has not run, m_k < 2 or m_k > 2 pop_size_k, a chromosome
+ * outside [0, nchrom), and sfs2d_plan_spectra's refusals of the selection; SFS2D_E_NOMEM: ngroups rows do not fit;
+ * SFS2D_E_CAP: B leaves fewer than 8 fraction bits.
+ * The reference has no projection (its users extract the outlier windows' SNPs and run easySFS on them). */
+#define SFS2D_PROJ_ROW_WORDS(m1, m2) (((m1) + 1) * ((m2) + 1) + 2)
+int sfs2d_plan_project(sfs2d_plan* plan, int32_t m1, int32_t m2, const int64_t* rec, const int32_t* grp, int64_t nsel,
+                       int64_t ngroups, int64_t* out_dev, int32_t* e_out);
+/* copy the last sfs2d_plan_project call's rows to host (synchronises) as doubles, x * 2^-e: out_host ngroups x
+ * (m1 + 1)(m2 + 1) grids, used / dropped ngroups counts each.  *ngroups_out, *words_per_group: the call's groups and
+ * grid words; SFS2D_E_CAP: cap_groups below the former; SFS2D_E_ARG: no project call since the plan was created */
+int sfs2d_plan_project_read(sfs2d_plan* plan, double* out_host, int64_t* used, int64_t* dropped, int64_t cap_groups,
+                            int64_t* ngroups_out, int64_t* words_per_group);
+/* the weights h(j; n, a, m), j = 0 .. m, into w_out (m + 1 doubles): host only, no device or ctx, the source the
+ * kernel evaluates (ln k! table, one exp per weight; exactly 0 outside the support, exactly 1 on a support of one
+ * bin).  SFS2D_E_ARG: a > n, m > n, n > 510, a negative argument or w_out == NULL */
+int sfs2d_project_weights(int32_t n, int32_t a, int32_t m, double* w_out);
 /* launch geometry (threads per grid) of k_prep and of the scan kernel: matches the Grid_Size column
  * of rocprofv3 kernel traces, so profiles can be joined to a plan */
 int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* scan_threads);
