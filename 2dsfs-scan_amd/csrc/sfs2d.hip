@@ -115,6 +115,7 @@ struct sfs2d_ctx {
   double* d_lf = nullptr;   // ln k!, k < PROJ_LF: k_proj_win's weights (allocated by the first sfs2d_plan_project)
   double* d_hw = nullptr;   // 1 / h(n), h(n) = sum_{i=1}^{n-1} 1/i, for n < RCPN (0 below n = 2): k_div_win's Watterson terms
   hipEvent_t stagger = nullptr;   // sfs2d_plan_run_streams: the first run's k_prep, awaited by the second stream
+  bool capturing = false;         // sfs2d_graph_create is capturing: the runs it enqueues execute at sfs2d_graph_launch
   std::string err;
   std::mutex err_mu;
 };
@@ -281,8 +282,13 @@ struct sfs2d_plan {
   int64_t proj_groups = -1, proj_roww = 0;   // groups and row words of the last call (-1: none yet)
   int proj_e = 0;                        // its fixed point 2^-e
   int64_t maxsnp = 0;                    // plan_create's bound on the SNPs of one record (Fst's e, P16)
-  uint64_t null_tab_runs = ~0ull;        // fused / sliced plans: the run whose tables of EVERY chromosome are in
-                                         // d_tab / d_lp / d_head (their scans keep all but one chromosome's in LDS)
+  // runs enqueued for EXECUTION, apart from `runs` (the parity of the buffers the next enqueued run takes): a run
+  // enqueued into a graph capture counts when the graph is launched (sfs2d_graph_launch), not at the capture.  The
+  // "last run" of sfs2d_plan_read and the post-scan calls is the last of these; 0: the plan has no records yet.
+  uint64_t done = 0;
+  uint64_t null_tab_runs = ~0ull;        // fused / sliced plans: the executed run (`done`) whose tables of EVERY
+                                         // chromosome are in d_tab / d_lp / d_head (their scans keep all but one
+                                         // chromosome's in LDS)
 };
 
 namespace {
@@ -715,7 +721,7 @@ int launch_scan_any(sfs2d_plan* pl, sfs2d_window* out) {
 int launch_attached(sfs2d_plan* a) {
   const sfs2d_data* d = a->data;
   const uint32_t ns = (uint32_t)a->nslots;
-  if (!ns) { a->runs++; return 0; }
+  if (!ns) { a->runs++; a->done += a->ctx->capturing ? 0 : 1; return 0; }
   const dim3 g((ns + 255) / 256);
   if (a->regions)
     hipLaunchKernelGGL(k_slots_regions, g, dim3(256), 0, CTX_STREAM(a->ctx), d->pos, d->d_chrom_off, a->d_slot_base,
@@ -734,6 +740,7 @@ int launch_attached(sfs2d_plan* a) {
   const int rc = launch_scan_any(a, a->d_out);
   a->last_out = a->d_out;
   a->runs++;
+  if (!a->ctx->capturing) a->done++;
   return rc;
 }
 
@@ -1769,6 +1776,7 @@ int sfs2d_plan_run_phase(sfs2d_plan* pl, int phase, sfs2d_window* out_dev) {
     if ((rc = launch_scan_any(pl, out))) return rc;
     pl->last_out = out;
     pl->runs++;
+    if (!ctx->capturing) pl->done++;
   }
   for (auto& e : pl->kev) e = nullptr;
   if (te && phase == 1) pl->tpend = te;   // (counted when its phase 2 has run)
@@ -1937,6 +1945,8 @@ struct sfs2d_graph {
   std::vector<hipGraphExec_t> execs;
   std::vector<sfs2d_plan*> plans;
   std::vector<int64_t> par;
+  std::vector<sfs2d_window*> outs;   // where a replay leaves each plan's records (the plan's last_out after a launch)
+  uint64_t per_plan = 0;             // runs of every plan in one replay
 };
 
 static void graph_free(sfs2d_graph* g) {
@@ -1971,6 +1981,9 @@ int sfs2d_graph_create(sfs2d_plan* const* plans, void* const* streams, sfs2d_win
   hipStream_t saved = CTX_STREAM(ctx);
   int rc = 0;
   hipError_t e = hipSuccess;
+  // the capture enqueues nothing for execution: the plans' last runs, and where their records are, stay what they were
+  std::vector<sfs2d_window*> last((size_t)nplans);
+  for (int k = 0; k < nplans; ++k) last[(size_t)k] = plans[k]->last_out;
   // a slots_once plan that has not run yet writes its slot table now, on its stream and ahead of the capture
   // (synchronised below): the graphs then hold no slot kernel
   for (int k = 0; k < nplans && k < nruns && e == hipSuccess; ++k)
@@ -1985,10 +1998,12 @@ int sfs2d_graph_create(sfs2d_plan* const* plans, void* const* streams, sfs2d_win
     if (e == hipSuccess) e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) break;
     ctx->stream = s;
+    ctx->capturing = true;
     for (int i = 0; i < nruns && !rc; ++i) {
       const int k = i % nplans;
       if ((hipStream_t)streams[k] == s) rc = sfs2d_plan_run_phase(plans[k], 0, outs ? outs[k] : nullptr);
     }
+    ctx->capturing = false;
     hipGraph_t gr = nullptr;
     e = hipStreamEndCapture(s, &gr);
     g->graphs.push_back(gr);
@@ -1998,10 +2013,15 @@ int sfs2d_graph_create(sfs2d_plan* const* plans, void* const* streams, sfs2d_win
     if (rc || e != hipSuccess) break;
   }
   ctx->stream = saved;
+  for (int k = 0; k < nplans; ++k) {
+    g->outs.push_back(outs && outs[k] ? outs[k] : plans[k]->d_out);
+    plans[k]->last_out = last[(size_t)k];
+  }
   if (rc || e != hipSuccess) {
     graph_free(g);
     return rc ? rc : set_err(ctx, SFS2D_E_HIP, std::string("graph capture: ") + hipGetErrorString(e));
   }
+  g->per_plan = (uint64_t)(nruns / nplans);
   for (int k = 0; k < nplans; ++k) {
     g->plans.push_back(plans[k]);
     g->par.push_back(plans[k]->runs & 1);
@@ -2017,8 +2037,16 @@ int sfs2d_graph_launch(sfs2d_graph* g, int nlaunch) {
     if ((g->plans[k]->runs & 1) != g->par[k])
       return set_err(ctx, SFS2D_E_ARG, "a captured plan ran an odd number of times since the capture");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  for (int i = 0; i < nlaunch; ++i)
+  for (int i = 0; i < nlaunch; ++i) {
     for (size_t j = 0; j < g->execs.size(); ++j) HIPCHK(ctx, hipGraphLaunch(g->execs[j], g->streams[j]));
+    // the replay's runs are every captured plan's last runs now (host bookkeeping alone: nothing is synchronised)
+    for (size_t k = 0; k < g->plans.size(); ++k) {
+      sfs2d_plan* pl = g->plans[k];
+      pl->done += g->per_plan;
+      pl->last_out = g->outs[k];
+      for (sfs2d_plan* a : pl->attached) a->done += g->per_plan;
+    }
+  }
   return 0;
 }
 
@@ -2127,6 +2155,8 @@ int sfs2d_plan_fst_read(sfs2d_plan* pl, double* out_host, int64_t cap) {
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   if (!pl->fst) return set_err(ctx, SFS2D_E_ARG, "plan was created without SFS2D_F_FST");
+  if (pl->done == 0)
+    return set_err(ctx, SFS2D_E_ARG, "Fst read before the plan's first run (a captured run counts once its graph is launched)");
   if (cap < pl->nslots) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
   if (pl->nslots && !out_host) return SFS2D_E_ARG;
   if (pl->nslots)
@@ -2184,6 +2214,9 @@ int sfs2d_plan_read(sfs2d_plan* pl, sfs2d_window* out_host, int64_t cap, int64_t
   if (!pl || !nrec_out) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   *nrec_out = pl->nrec;
+  if (pl->done == 0)
+    return set_err(ctx, SFS2D_E_ARG, "read before the plan's first run (no records yet; a captured run counts once its graph "
+                                     "is launched)");
   if (cap < pl->nrec) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
   if (pl->nrec && !out_host) return SFS2D_E_ARG;
   const sfs2d_window* src = pl->last_out ? pl->last_out : pl->d_out;
@@ -2208,7 +2241,7 @@ namespace {
 //           which the next scan would do anyway, so it runs once per plan run (null_tab_runs).
 int null_tables(sfs2d_plan* pl) {
   sfs2d_ctx* ctx = pl->ctx;
-  if (!pl->do_bg || !(pl->fused || pl->sliced) || pl->null_tab_runs == pl->runs) return 0;
+  if (!pl->do_bg || !(pl->fused || pl->sliced) || pl->null_tab_runs == pl->done) return 0;
   const size_t lp = (size_t)((pl->runs - 1) & 1);   // parity of the last run
   if (pl->fused) {
     hipLaunchKernelGGL(k_bg_slice, dim3((unsigned)pl->slices.size() + 1, (unsigned)pl->nbg), dim3(KBLOCK), 0, CTX_STREAM(ctx),
@@ -2222,7 +2255,7 @@ int null_tables(sfs2d_plan* pl) {
                        pl->nleaves, pl->d_nodes, pl->nnodes, pl->nlevels);
   }
   HIPCHK(ctx, hipGetLastError());
-  pl->null_tab_runs = pl->runs;
+  pl->null_tab_runs = pl->done;
   return 0;
 }
 
@@ -2275,7 +2308,9 @@ int sfs2d_plan_null_run_blocks(sfs2d_plan* pl, const sfs2d_null_params* np, int6
   if (block < 1 || block > 0xffffffffll)
     return set_err(ctx, SFS2D_E_ARG, "null run: block length " + std::to_string(block) + " must be in [1, 2^32)");
   if (pl->base) return set_err(ctx, SFS2D_E_ARG, "null run on an attached plan: use its base plan (same data, same tables)");
-  if (pl->runs == 0) return set_err(ctx, SFS2D_E_ARG, "null run before the plan's first run (no background tables yet)");
+  if (pl->done == 0)
+    return set_err(ctx, SFS2D_E_ARG, "null run before the plan's first run (no background tables yet; a captured run counts "
+                                     "once its graph is launched)");
   if (np->replicates < 1) return set_err(ctx, SFS2D_E_ARG, "null run: replicates must be >= 1");
   if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "null run: data set too large for 32-bit SNP indices");
   pl->ntask_h.resize((size_t)ntasks);
@@ -2352,7 +2387,7 @@ int sfs2d_plan_diversity(sfs2d_plan* pl, sfs2d_diversity* out_dev) {
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   const sfs2d_data* d = pl->data;
-  if (pl->runs == 0)
+  if (pl->done == 0)   // (a run that was only captured has not executed: sfs2d_graph_launch counts it)
     return set_err(ctx, SFS2D_E_ARG, pl->base ? "diversity before the base plan's first run (an attached plan has no records yet)"
                                               : "diversity before the plan's first run (no records yet)");
   if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "diversity: data set too large for 32-bit SNP indices");
@@ -2401,7 +2436,7 @@ int sfs2d_plan_spectra(sfs2d_plan* pl, const int64_t* rec, const int32_t* grp, i
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   const sfs2d_data* d = pl->data;
-  if (pl->runs == 0)
+  if (pl->done == 0)   // (a run that was only captured has not executed: sfs2d_graph_launch counts it)
     return set_err(ctx, SFS2D_E_ARG, pl->base ? "spectra before the base plan's first run (an attached plan has no records yet)"
                                               : "spectra before the plan's first run (no records yet)");
   if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "spectra: data set too large for 32-bit SNP indices");
@@ -2538,7 +2573,7 @@ int sfs2d_plan_project(sfs2d_plan* pl, int32_t m1, int32_t m2, const int64_t* re
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   const sfs2d_data* d = pl->data;
-  if (pl->runs == 0)
+  if (pl->done == 0)   // (a run that was only captured has not executed: sfs2d_graph_launch counts it)
     return set_err(ctx, SFS2D_E_ARG, pl->base ? "project before the base plan's first run (an attached plan has no records yet)"
                                               : "project before the plan's first run (no records yet)");
   if (m1 < 2 || m1 > pl->K.n1 || m2 < 2 || m2 > pl->K.n2)
@@ -2728,6 +2763,7 @@ int sfs2d_plan_time(sfs2d_plan* pl, int iters, double* ms_run, double* ms_k1, do
     HIPCHK(ctx, hipEventRecord(pl->ev[2], st));
     if ((rc = launch_scan_any(pl, pl->d_out))) return rc;
     pl->runs++;
+    pl->done++;
     HIPCHK(ctx, hipEventRecord(pl->ev[3], st));
     HIPCHK(ctx, hipEventSynchronize(pl->ev[3]));
     float a = 0, b = 0, c = 0, d = 0;

@@ -508,7 +508,10 @@ class RunGraph:
         self.eng, self.h, self.plans, self.runs = eng, h, plans, runs
 
     def launch(self, n: int = 1):
-        """Replay n times, on the capture streams (each replay after the stream's earlier work)."""
+        """Replay n times, on the capture streams (each replay after the stream's earlier work).  The replay's runs
+        are the captured plans' last runs from here on: once the capture streams are synchronised, ``read`` /
+        ``read_fst`` / ``null_run`` / ``diversity`` / ``spectra`` / ``project`` work on them (the capture alone is
+        no run: a plan that was only captured is refused like one that has not run)."""
         self.eng.check(self.eng.lib.sfs2d_graph_launch(self.h, int(n)))
 
     def close(self):

@@ -206,14 +206,24 @@ int sfs2d_plan_run_streams(sfs2d_plan* const* plans, void* const* streams, sfs2d
  * (every plan runs an even number of times per replay, so its buffer parity is unchanged); streams
  * non-null; no plan with timing on or attached.  The outputs are fixed at capture.  Replays run on the
  * capture streams, each after that stream's earlier work, without run_streams' staggered start.  A launch
- * fails with SFS2D_E_ARG when a captured plan ran an odd number of times since the capture.  Not a
+ * fails with SFS2D_E_ARG when a captured plan ran an odd number of times since the capture.
+ * The capture enqueues nothing for execution: it leaves every plan's last run, and where that run's records are,
+ * as they were, and a plan that was created and captured but never run or replayed has NO last run (sfs2d_plan_read,
+ * _fst_read and the post-scan calls refuse it like a plan that has not run).  A replay counts: after
+ * sfs2d_graph_launch the last run of every captured plan (and of the plans attached to it) is its last run of the
+ * replay, its records where the capture's outs put them, and sfs2d_plan_read, _fst_read, sfs2d_plan_null_run(_blocks),
+ * _diversity, _spectra and _project work on it once the capture streams are synchronised (the launch only enqueues and
+ * keeps host-side count of the runs; it synchronises nothing).  Not a
  * reference interface: repeated scans of the same data (the bench's loops; replicate loops as
  * sims_scan.py:593-644). */
 int sfs2d_graph_create(sfs2d_plan* const* plans, void* const* streams, sfs2d_window* const* outs, int nplans,
                        int nruns, sfs2d_graph** out);
 int sfs2d_graph_launch(sfs2d_graph* graph, int nlaunch);
 int sfs2d_graph_destroy(sfs2d_graph* graph);
-/* copy the last run's records to host (synchronises the stream) */
+/* copy the last run's records to host (synchronises the stream).  The last run is the last one enqueued for
+ * execution, however it was enqueued: sfs2d_plan_run (its out_dev or the plan's own buffer), _run_many, _run_streams,
+ * phases 1 + 2 of sfs2d_plan_run_phase, sfs2d_plan_time, or a replay by sfs2d_graph_launch (the capture's outs).
+ * SFS2D_E_ARG: a plan that has not run -- a capture alone is not a run */
 int sfs2d_plan_read(sfs2d_plan* plan, sfs2d_window* out_host, int64_t cap, int64_t* nrec_out);
 /* device pointers of the plan's per-chromosome background histogram replicas (uint32), for a
  * multi-GPU all-reduce between sfs2d_plan_run_phase(plan, 1) and (plan, 2). */
@@ -236,7 +246,8 @@ int sfs2d_plan_bg_exchange(sfs2d_plan* plan, uint32_t* host_repl, uint32_t* host
  * Both are enqueued on the ctx stream (order the collective against it). */
 int sfs2d_plan_bg_rows_dev(sfs2d_plan* plan, int64_t* d_rows, int64_t row_stride);
 int sfs2d_plan_bg_rows_set_dev(sfs2d_plan* plan, const int64_t* d_rows, int64_t row_stride);
-/* Fst of the last run per window slot (NaN: no qualifying SNP / empty slot); plans with SFS2D_F_FST */
+/* Fst of the last run (as sfs2d_plan_read defines it) per window slot (NaN: no qualifying SNP / empty slot); plans
+ * with SFS2D_F_FST; SFS2D_E_ARG: a plan that has not run */
 int sfs2d_plan_fst_read(sfs2d_plan* plan, double* out_host, int64_t cap);
 int sfs2d_plan_fst_buffer(sfs2d_plan* plan, void** dev_ptr, int64_t* nslots);
 /* Fst output of the following runs: a caller-owned device buffer of >= nslots doubles (NULL = the plan-owned
@@ -319,7 +330,10 @@ int sfs2d_plan_attach_regions(sfs2d_plan* base, const sfs2d_params* params, cons
  * end = m, the counts, SFS2D_W_BG*_ZERO flags and T's as the scan writes them.  The drawn windows are never
  * stored.  tasks: ntasks (pool, m) pairs on the host; out_dev: ntasks * replicates records on the device
  * (NULL = plan-owned, read with sfs2d_plan_null_read).  Enqueued on the ctx stream after the plan's last run,
- * which it leaves as it found it (the next run's records and Fst are byte-equal).  SFS2D_E_ARG, with the
+ * which it leaves as it found it (the next run's records and Fst are byte-equal).  The last run is sfs2d_plan_read's:
+ * however it was enqueued, a replay by sfs2d_graph_launch included (the null completes the background tables again
+ * after every replay, as after every run), and after a phase-split run the backgrounds are the exchanged rows; a
+ * plan that was only captured has not run.  SFS2D_E_ARG, with the
  * reason in sfs2d_last_error: a plan that has not run, an attached plan (use its base: same data, same
  * tables), a pool out of range, pool -1 on a per-chromosome plan, an empty pool, m < 1, replicates < 1;
  * SFS2D_E_CAP: more than 2^26 records in one call, or sfs2d_plan_null_read's cap below the record count.
@@ -328,7 +342,7 @@ int sfs2d_plan_attach_regions(sfs2d_plan* base, const sfs2d_params* params, cons
 typedef struct { uint64_t seed; uint32_t replicates; } sfs2d_null_params;
 int sfs2d_plan_null_run(sfs2d_plan* plan, const sfs2d_null_params* np, const int64_t* tasks, int64_t ntasks,
                         sfs2d_window* out_dev);
-/* The block null: sfs2d_plan_null_run with runs of consecutive SNPs resampled instead of single SNPs, so that a
+/* The block null: sfs2d_plan_null_run (its last run and its refusals included) with runs of consecutive SNPs resampled instead of single SNPs, so that a
  * replicate window keeps the linkage of its pool ("blocks").  One block length `block` for
  * the call, 1 <= block < 2^32.  Task (pool, m), pool range [lo, lo + n), replicate r: nblk = ceil(m / block)
  * blocks; block i starts at s_i = mulhi64(x64, n), x64 being what draw i of sfs2d_plan_null_run uses
@@ -367,7 +381,8 @@ typedef struct {
  * the ctx stream; out_dev: device buffer of sfs2d_plan_num_records records (NULL = plan-owned, read with
  * sfs2d_plan_diversity_read).  Any plan that has run, attached plans included (their own records, their base's
  * data); reads the records, the counts and (filtered plans) the per-SNP bins, writes out_dev alone: a following
- * run or null run finds everything as it was.  SFS2D_E_ARG, with the reason in sfs2d_last_error: a plan that
+ * run or null run finds everything as it was.  The last run is sfs2d_plan_read's (a replay by sfs2d_graph_launch
+ * counts, a capture alone does not).  SFS2D_E_ARG, with the reason in sfs2d_last_error: a plan that
  * has not run.  The reference has no such statistic (its users join pixy's or scikit-allel's by window label). */
 int sfs2d_plan_diversity(sfs2d_plan* plan, sfs2d_diversity* out_dev);
 /* copy the last sfs2d_plan_diversity call's records to host (synchronises); SFS2D_E_CAP: cap below the record
@@ -392,7 +407,8 @@ int sfs2d_plan_diversity_read(sfs2d_plan* plan, sfs2d_diversity* out_host, int64
  * sfs2d_plan_spectra_read), zeroed by the call.  Enqueued on the ctx stream after the plan's last run; any plan that
  * has run, attached, sliding, regions and SNP-count plans included (their own records, the base's data and bins).
  * Reads the records, the counts and (filtered plans) the per-SNP bins, writes out_dev alone: a following run, null
- * run or diversity call finds everything as it was.  Integer sums: two calls give byte-equal rows.
+ * run or diversity call finds everything as it was.  Integer sums: two calls give byte-equal rows.  The last run is
+ * sfs2d_plan_read's (a replay by sfs2d_graph_launch counts, a capture alone does not).
  * SFS2D_E_ARG, the reason in sfs2d_last_error: a plan that has not run, nsel < 0, ngroups < 1, a record index
  * outside [0, nrec), a group outside [0, ngroups), grp == NULL with rec != NULL, rec == NULL with nsel != nrec;
  * SFS2D_E_NOMEM: ngroups rows do not fit.
@@ -427,7 +443,8 @@ int sfs2d_plan_spectra_read(sfs2d_plan* plan, int64_t* out_host, int64_t cap_wor
  * names the whole chromosome c of the plan's data set, [chrom_off[c], chrom_off[c + 1]), under the same membership:
  * a projected per-chromosome background on any plan kind.  Enqueued on the ctx stream after the plan's last run;
  * reads the records, the counts and (filtered plans) the per-SNP bins, writes out_dev alone: a following run, null
- * run, diversity or spectra call finds everything as it was.
+ * run, diversity or spectra call finds everything as it was.  The last run is sfs2d_plan_read's (a replay by
+ * sfs2d_graph_launch counts, a capture alone does not).
  * SFS2D_E_ARG, the reason in sfs2d_last_error: a plan that has not run, m_k < 2 or m_k > 2 pop_size_k, a chromosome
  * outside [0, nchrom), and sfs2d_plan_spectra's refusals of the selection; SFS2D_E_NOMEM: ngroups rows do not fit;
  * SFS2D_E_CAP: B leaves fewer than 8 fraction bits.

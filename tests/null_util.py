@@ -1,9 +1,13 @@
 """Shared by the bootstrap-null tests: oracle-evaluated twins of the device's null records."""
 import numpy as np
 
+import golden_util as gu
 from oracle import sfs_oracle as O
 from sfs2d import _lib as L
 from sfs2d import null as N
+
+INTS = ("chrom", "wid", "begin", "end", "snp_count", "n2", "n2_all", "n1a", "n1b", "flags")
+T_FLOOR = 1e-2   # T's below it are compared as if they were 1e-2 (test_null_gpu.py's module docstring)
 
 
 def oracle_records(p, wins, cfg, bg_of, chrom_of=lambda w: w[0], wid_of=lambda w: w[1]):
@@ -38,6 +42,26 @@ def null_twin(p, tasks, replicates, seed, cfg, bg_of):
     and the oracle: (records, replicate data set, windows)."""
     q, wins = N.resample(p, tasks, replicates, seed)
     return oracle_records(q, wins, cfg, bg_of), q, wins
+
+
+def check(got, want, wide=False):
+    """wide (windows of 65,536 SNPs): S and N ln N are ~3e5 there, each a sum of tens of rounded terms, so
+    either side's absolute error is up to ~100 eps N ln N = 3e-9 (seen: 7e-11 on T1D = 0.18): the relative
+    1e-10 is then taken of max(|T|, 1e-4 N ln N)."""
+    assert len(got) == len(want) > 0
+    for f in INTS:
+        bad = np.nonzero(got[f] != want[f])[0]
+        assert bad.size == 0, (f, bad[:5], got[f][bad[:5]], want[f][bad[:5]], got[["chrom", "wid", "end"]][bad[:5]])
+    assert np.array_equal(N.valid_mask(got), N.valid_mask(want))
+    v = N.valid_mask(want)
+    nvalid = 0
+    for s, (f, nf) in enumerate((("t2d", "n2"), ("t1d_p1", "n1a"), ("t1d_p2", "n1b"))):
+        for i in np.nonzero(v[s])[0]:
+            n = float(want[nf][i])
+            scale = max(T_FLOOR, 1e-4 * n * np.log(n)) if wide else T_FLOOR
+            assert gu.close(float(got[f][i]), float(want[f][i]), scale=scale), (f, i, got[i], want[i])
+            nvalid += 1
+    return nvalid
 
 
 def ks_uniform(pv):

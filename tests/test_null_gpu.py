@@ -34,8 +34,8 @@ MS = [1, 2, 63, 64, 65, 129, 700]
 R, SEED = 37, 5
 W = 20000
 VT = "intron_variant"
-INTS = ("chrom", "wid", "begin", "end", "snp_count", "n2", "n2_all", "n1a", "n1b", "flags")
-T_FLOOR = 1e-2   # see the module docstring
+INTS = U.INTS
+T_FLOOR = U.T_FLOOR   # see the module docstring
 _DATA, _TWIN = {}, {}
 
 
@@ -74,24 +74,7 @@ def _twin(n1p, n2p, fold=True, vt=None, start=None, end=None, bg=None, pools=(0,
     return _TWIN[key]
 
 
-def _check(got, want, wide=False):
-    """wide (windows of 65,536 SNPs): S and N ln N are ~3e5 there, each a sum of tens of rounded terms, so
-    either side's absolute error is up to ~100 eps N ln N = 3e-9 (seen: 7e-11 on T1D = 0.18): the relative
-    1e-10 is then taken of max(|T|, 1e-4 N ln N)."""
-    assert len(got) == len(want) > 0
-    for f in INTS:
-        bad = np.nonzero(got[f] != want[f])[0]
-        assert bad.size == 0, (f, bad[:5], got[f][bad[:5]], want[f][bad[:5]], got[["chrom", "wid", "end"]][bad[:5]])
-    assert np.array_equal(N.valid_mask(got), N.valid_mask(want))
-    v = N.valid_mask(want)
-    nvalid = 0
-    for s, (f, nf) in enumerate((("t2d", "n2"), ("t1d_p1", "n1a"), ("t1d_p2", "n1b"))):
-        for i in np.nonzero(v[s])[0]:
-            n = float(want[nf][i])
-            scale = max(T_FLOOR, 1e-4 * n * np.log(n)) if wide else T_FLOOR
-            assert gu.close(float(got[f][i]), float(want[f][i]), scale=scale), (f, i, got[i], want[i])
-            nvalid += 1
-    return nvalid
+_check = U.check
 
 
 def _engine():
