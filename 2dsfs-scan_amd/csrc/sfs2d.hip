@@ -16,6 +16,8 @@
 // spectra themselves, summed into groups, as int64 rows; it too writes its own output alone.
 // sfs2d_plan_project enqueues k_proj_win (sfs2d_proj.hpp) over chosen records or whole chromosomes: the joint
 // spectrum projected down to a common sample size, as int64 fixed-point rows; it writes its own output alone.
+// sfs2d_plan_project_scan enqueues k_proj_win over the background chromosomes, k_proj_lp and k_proj_scan
+// (sfs2d_projscan.hpp): T2D / T1D of every record at a common sample size, the window grids in LDS alone.
 // All device state a run touches (slot table, background replicas and counters, LDS) is left
 // zeroed by the run itself, so plans replay without memsets.
 #include <hip/hip_runtime.h>
@@ -40,6 +42,7 @@
 #include "sfs2d_div.hpp"
 #include "sfs2d_spec.hpp"
 #include "sfs2d_proj.hpp"
+#include "sfs2d_projscan.hpp"
 
 using namespace sfs2dk;
 
@@ -281,6 +284,18 @@ struct sfs2d_plan {
   const int64_t* proj_last = nullptr;
   int64_t proj_groups = -1, proj_roww = 0;   // groups and row words of the last call (-1: none yet)
   int proj_e = 0;                        // its fixed point 2^-e
+  // the projected scan (sfs2d_plan_project_scan): the background chromosomes' selection, rows and ln tables, and
+  // the plan-owned records
+  std::vector<ProjSel> pscan_sel_h;
+  ProjSel* d_pscan_sel = nullptr;
+  size_t pscan_sel_cap = 0;
+  unsigned long long* d_pscan_bg = nullptr;
+  size_t pscan_bg_cap = 0;               // ... in words
+  double* d_pscan_lp = nullptr;
+  size_t pscan_lp_cap = 0;
+  sfs2d_projstat* d_pscan = nullptr;
+  const sfs2d_projstat* pscan_last = nullptr;
+  int64_t pscan_nrec = -1;               // records of the last call (-1: none yet)
   int64_t maxsnp = 0;                    // plan_create's bound on the SNPs of one record (Fst's e, P16)
   // runs enqueued for EXECUTION, apart from `runs` (the parity of the buffers the next enqueued run takes): a run
   // enqueued into a graph capture counts when the graph is launched (sfs2d_graph_launch), not at the capture.  The
@@ -336,6 +351,7 @@ void plan_free(sfs2d_plan* p) {
   hipFree(p->d_ntask); hipFree(p->d_null); hipFree(p->d_div);
   hipFree(p->d_spec_sel); hipFree(p->d_spec);
   hipFree(p->d_proj_sel); hipFree(p->d_proj);
+  hipFree(p->d_pscan_sel); hipFree(p->d_pscan_bg); hipFree(p->d_pscan_lp); hipFree(p->d_pscan);
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->tev) if (e) hipEventDestroy(e);
 }
@@ -444,6 +460,16 @@ struct ProjWin {   // k_proj_win<CNT, LDSH>
   static constexpr ProjWin at(int i) { return {bool(i & 1), bool(i & 2)}; }
   constexpr bool legal() const { return true; }
   template <int I> static constexpr Fn kernel() { constexpr ProjWin s = at(I); return k_proj_win<s.cnt, s.ldsh>; }
+};
+
+struct ProjScan {   // k_proj_scan<CNT>
+  bool cnt;
+  using Fn = decltype(&k_proj_scan<true>);
+  static constexpr int N = 2;
+  constexpr int index() const { return cnt; }
+  static constexpr ProjScan at(int i) { return {bool(i & 1)}; }
+  constexpr bool legal() const { return true; }
+  template <int I> static constexpr Fn kernel() { constexpr ProjScan s = at(I); return k_proj_scan<s.cnt>; }
 };
 
 // entry I of family S's table: its kernel, instantiated only where the selection is legal
@@ -2568,6 +2594,29 @@ int sfs2d_project_weights(int32_t n, int32_t a, int32_t m, double* w_out) {
   return 0;
 }
 
+namespace {
+// k_proj_win's row histogram in LDS: whether `lds` bytes of it fit a CU beside the table of ln k!, opting the
+// family in above the default limit (a refusal selects the global-atomic instantiations)
+bool proj_win_ldsh(sfs2d_ctx* ctx, size_t lds) {
+  bool ldsh = lds + 4096 <= 160 * 1024;
+  if (ldsh && lds > 64 * 1024) {
+    static std::mutex mu;
+    static std::map<int, size_t> granted;   // device -> the dynamic LDS its k_proj_win instantiations may take
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& have = granted[ctx->device];
+    if (lds > have) {
+      if (set_max_lds<ProjWin>(lds) != hipSuccess) {
+        (void)hipGetLastError();
+        ldsh = false;
+      } else {
+        have = lds;
+      }
+    }
+  }
+  return ldsh;
+}
+}  // namespace
+
 int sfs2d_plan_project(sfs2d_plan* pl, int32_t m1, int32_t m2, const int64_t* rec, const int32_t* grp, int64_t nsel,
                        int64_t ngroups, int64_t* out_dev, int32_t* e_out) {
   if (!pl) return SFS2D_E_ARG;
@@ -2676,21 +2725,7 @@ int sfs2d_plan_project(sfs2d_plan* pl, int32_t m1, int32_t m2, const int64_t* re
   // the kernels opt in, and a refusal selects the global-atomic instantiations.  The projection changes from call to
   // call and the limit belongs to the kernels, not to a plan: per device it only grows.
   const size_t lds = sizeof(unsigned long long) * (size_t)roww;
-  bool ldsh = lds + 4096 <= 160 * 1024;
-  if (ldsh && lds > 64 * 1024) {
-    static std::mutex mu;
-    static std::map<int, size_t> granted;   // device -> the dynamic LDS its k_proj_win instantiations may take
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& have = granted[ctx->device];
-    if (lds > have) {
-      if (set_max_lds<ProjWin>(lds) != hipSuccess) {
-        (void)hipGetLastError();
-        ldsh = false;
-      } else {
-        have = lds;
-      }
-    }
-  }
+  const bool ldsh = proj_win_ldsh(ctx, lds);
   HIPCHK(ctx, hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)words, st));
   pl->proj_last = out;
   pl->proj_groups = ngroups;
@@ -2740,6 +2775,153 @@ int sfs2d_plan_project_read(sfs2d_plan* pl, double* out_host, int64_t* used, int
     used[g] = r[ngrid];
     dropped[g] = r[ngrid + 1];
   }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------ projected scan
+
+int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_chrom, sfs2d_projstat* out_dev,
+                            int32_t* e_out, int32_t* e_bg_out) {
+  if (!pl) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  const sfs2d_data* d = pl->data;
+  if (pl->done == 0)   // (a run that was only captured has not executed: sfs2d_graph_launch counts it)
+    return set_err(ctx, SFS2D_E_ARG, pl->base ? "project_scan before the base plan's first run (an attached plan has no records yet)"
+                                              : "project_scan before the plan's first run (no records yet)");
+  if (pl->prm.bg_mode == SFS2D_BG_SUPPLIED)
+    return set_err(ctx, SFS2D_E_ARG, "project_scan: a plan with a supplied background has no projected background "
+                                     "(only per-chromosome plans; bg_chrom names one chromosome for every record)");
+  if (m1 < 2 || m1 > pl->K.n1 || m2 < 2 || m2 > pl->K.n2)
+    return set_err(ctx, SFS2D_E_ARG, "project_scan: (m1, m2) = (" + std::to_string(m1) + ", " + std::to_string(m2) +
+                                         ") outside [2, " + std::to_string(pl->K.n1) + "] x [2, " + std::to_string(pl->K.n2) + "]");
+  if (bg_chrom < -1 || bg_chrom >= d->nchrom)
+    return set_err(ctx, SFS2D_E_ARG, "project_scan: bg_chrom " + std::to_string(bg_chrom) + " outside [-1, " +
+                                         std::to_string(d->nchrom) + ")");
+  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project_scan: data set too large for 32-bit SNP indices");
+  if (pl->nrec > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project_scan: more than 2^32 - 1 records");
+  const int64_t ngrid = (int64_t)(m1 + 1) * (m2 + 1), roww = ngrid + 2, lpw = ngrid + (m1 + 1) + (m2 + 1);
+  // the window grid, its marginals and sums in LDS beside the 4 KB table: there is no global-memory variant (a
+  // grid per window in HBM is what this call avoids)
+  const size_t lds = sizeof(unsigned long long) * pscan_lds_words((uint32_t)m1, (uint32_t)m2);
+  if (lds + 4096 > 160 * 1024)
+    return set_err(ctx, SFS2D_E_CAP, "project_scan: the (" + std::to_string(m1 + 1) + " x " + std::to_string(m2 + 1) +
+                                         ") window grid takes " + std::to_string(lds + 4096) +
+                                         " bytes of LDS, more than the 163840 of a compute unit");
+  auto fixed_point = [](int64_t B) {   // e = min(40, 62 - bitlen(B))
+    int b = 0;
+    while (b < 63 && (B >> b) != 0) ++b;
+    return std::min(40, 62 - b);
+  };
+  // windows: one record per grid; backgrounds: one chromosome entry per row (section 18's rule for such a call)
+  const int64_t per_rec = std::max<int64_t>(1, pl->maxsnp);
+  const int nbg = bg_chrom < 0 ? d->nchrom : 1;
+  int64_t per_bg = per_rec;
+  pl->pscan_sel_h.clear();
+  for (int g = 0; g < nbg; ++g) {
+    const int c = bg_chrom < 0 ? g : bg_chrom;
+    const int64_t cb = d->chrom_off[(size_t)c], ce = d->chrom_off[(size_t)c + 1];
+    for (int64_t s = cb; s < ce; s += PROJ_CHUNK)
+      pl->pscan_sel_h.push_back(ProjSel{0xffffffffu, (uint32_t)g, (uint32_t)s, (uint32_t)std::min<int64_t>(s + PROJ_CHUNK, ce)});
+    per_bg = std::max<int64_t>(per_bg, ce - cb);
+  }
+  const int e = fixed_point(per_rec), e_bg = fixed_point(per_bg);
+  if (e < 8 || e_bg < 8)
+    return set_err(ctx, SFS2D_E_CAP, "project_scan: up to " + std::to_string(e < 8 ? per_rec : per_bg) +
+                                         " SNPs in one grid leave fewer than 8 fraction bits in 64-bit sums");
+  if (e_out) *e_out = e;
+  if (e_bg_out) *e_bg_out = e_bg;
+  const size_t nsel = pl->pscan_sel_h.size();
+  if (nsel > 0xffffffffull) return set_err(ctx, SFS2D_E_ARG, "project_scan: more than 2^32 - 1 background pieces");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = CTX_STREAM(ctx);
+  if (!ctx->d_lf) {
+    int rc = dalloc(ctx, &ctx->d_lf, (size_t)PROJ_LF);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(ctx->d_lf, proj_lf_table(), sizeof(double) * PROJ_LF, hipMemcpyHostToDevice));
+  }
+  const size_t bgw = (size_t)nbg * (size_t)roww, lpn = (size_t)nbg * (size_t)lpw;
+  if (nsel > pl->pscan_sel_cap || bgw > pl->pscan_bg_cap || lpn > pl->pscan_lp_cap) {
+    HIPCHK(ctx, hipStreamSynchronize(st));   // an earlier call may still read what is replaced
+    auto grow = [&](auto** p, size_t* cap, size_t want) {
+      if (want <= *cap) return 0;
+      hipFree(*p);
+      *p = nullptr;
+      *cap = 0;
+      const int rc = dalloc(ctx, p, want);
+      if (rc) (void)hipGetLastError();
+      else *cap = want;
+      return rc;
+    };
+    int rc = grow(&pl->d_pscan_sel, &pl->pscan_sel_cap, nsel);
+    if (!rc) rc = grow(&pl->d_pscan_bg, &pl->pscan_bg_cap, bgw);
+    if (!rc) rc = grow(&pl->d_pscan_lp, &pl->pscan_lp_cap, lpn);
+    if (rc) return rc;
+  }
+  if (!out_dev && !pl->d_pscan && pl->nrec) {
+    int rc = dalloc(ctx, &pl->d_pscan, (size_t)pl->nrec);
+    if (rc) return rc;
+  }
+  if (lds + 4096 > 64 * 1024) {   // above the default limit the family opts in; per device the limit only grows
+    static std::mutex mu;
+    static std::map<int, size_t> granted;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& have = granted[ctx->device];
+    if (lds > have) {
+      if (set_max_lds<ProjScan>(lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(ctx, SFS2D_E_CAP, "project_scan: the device refuses " + std::to_string(lds) +
+                                             " bytes of dynamic LDS for k_proj_scan");
+      }
+      have = lds;
+    }
+  }
+  int rc = 0;
+  const ProjScan::Fn ks = variant(ctx, ProjScan{pl->cnt}, "k_proj_scan", &rc);
+  if (!ks) return rc;
+  sfs2d_projstat* out = out_dev ? out_dev : pl->d_pscan;
+  pl->pscan_last = out;
+  pl->pscan_nrec = pl->nrec;
+  if (pl->nrec == 0) return 0;
+  const sfs2d_window* recs = pl->last_out ? pl->last_out : pl->d_out;
+  // the background chromosomes' rows by k_proj_win (chromosome entries, as sfs2d_plan_project launches them) ...
+  HIPCHK(ctx, hipMemsetAsync(pl->d_pscan_bg, 0, sizeof(unsigned long long) * bgw, st));
+  if (nsel) {
+    HIPCHK(ctx, hipMemcpyAsync(pl->d_pscan_sel, pl->pscan_sel_h.data(), sizeof(ProjSel) * nsel, hipMemcpyHostToDevice, st));
+    const size_t wlds = sizeof(unsigned long long) * (size_t)roww;
+    const bool ldsh = proj_win_ldsh(ctx, wlds);
+    const ProjWin::Fn kw = variant(ctx, ProjWin{pl->cnt, ldsh}, "k_proj_win", &rc);
+    if (!kw) return rc;
+    const int per_cu = ldsh ? (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (wlds + 4096))) : 8;
+    const dim3 g((unsigned)std::min<int64_t>((int64_t)nsel, (int64_t)per_cu * ctx->ncu));
+    hipLaunchKernelGGL(kw, g, dim3(PROJ_BLOCK), ldsh ? wlds : 0, st, pl->K, d->counts, scan_src(pl), recs, pl->d_pscan_sel,
+                       ctx->d_lf, pl->d_pscan_bg, (uint32_t)nsel, (uint32_t)pl->nrec, (uint32_t)nbg, (uint32_t)d->n,
+                       (uint32_t)m1, (uint32_t)m2, std::ldexp(1.0, e_bg), 1ull << (62 - e_bg));
+    HIPCHK(ctx, hipGetLastError());
+  }
+  // ... their ln tables, and every record against its chromosome's
+  hipLaunchKernelGGL(k_proj_lp, dim3((unsigned)nbg), dim3(PROJ_BLOCK), 0, st, pl->d_pscan_bg, pl->d_pscan_lp, (uint32_t)m1,
+                     (uint32_t)m2, pl->K.fold);
+  HIPCHK(ctx, hipGetLastError());
+  const int per_cu = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds + 4096)));
+  const dim3 g((unsigned)std::min<int64_t>(pl->nrec, (int64_t)per_cu * ctx->ncu));
+  hipLaunchKernelGGL(ks, g, dim3(PROJ_BLOCK), lds, st, pl->K, d->counts, scan_src(pl), recs, ctx->d_lf, pl->d_pscan_lp, out,
+                     (uint32_t)pl->nrec, (uint32_t)nbg, (uint32_t)d->n, (uint32_t)m1, (uint32_t)m2, bg_chrom < 0 ? 0 : 1,
+                     std::ldexp(1.0, e), std::ldexp(1.0, -e), (uint32_t)e);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int sfs2d_plan_project_scan_read(sfs2d_plan* pl, sfs2d_projstat* out_host, int64_t cap, int64_t* nrec_out) {
+  if (!pl || !nrec_out) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  if (pl->pscan_nrec < 0) return set_err(ctx, SFS2D_E_ARG, "sfs2d_plan_project_scan_read before sfs2d_plan_project_scan");
+  *nrec_out = pl->pscan_nrec;
+  if (cap < pl->pscan_nrec) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
+  if (pl->pscan_nrec && !out_host) return SFS2D_E_ARG;
+  if (pl->pscan_nrec)
+    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->pscan_last, sizeof(sfs2d_projstat) * (size_t)pl->pscan_nrec,
+                               hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
+  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
   return 0;
 }
 

@@ -61,6 +61,7 @@ EXPORTS = [
     "sfs2d_plan_create_regions", "sfs2d_plan_attach_regions",
     "sfs2d_plan_spectra", "sfs2d_plan_spectra_read",
     "sfs2d_plan_project", "sfs2d_plan_project_read", "sfs2d_project_weights",
+    "sfs2d_plan_project_scan", "sfs2d_plan_project_scan_read",
 ]
 ABI_VERSION = 2   # SFS2D_ABI_VERSION of include/sfs2d.h
 
@@ -103,6 +104,15 @@ DIVERSITY_DTYPE = np.dtype([
     ("s1", "<u4"), ("s2", "<u4"), ("s1_full", "<u4"), ("s2_full", "<u4"), ("flags", "<u4"), ("reserved", "<u4"),
 ])
 assert DIVERSITY_DTYPE.itemsize == 80
+
+# sfs2d_projstat: T2D / T1D of one window at a common sample size, one per window record at the same index
+# (sfs2d_plan_project_scan); n2_fx / n1a_fx / n1b_fx: the three N as integers at the fixed point 2^-e
+PROJSTAT_DTYPE = np.dtype([
+    ("t2d", "<f8"), ("t1d_p1", "<f8"), ("t1d_p2", "<f8"),
+    ("n2_fx", "<i8"), ("n1a_fx", "<i8"), ("n1b_fx", "<i8"),
+    ("n_used", "<u4"), ("n_dropped", "<u4"), ("flags", "<u4"), ("e", "<u4"),
+])
+assert PROJSTAT_DTYPE.itemsize == 64
 
 _lib = None
 
@@ -187,6 +197,8 @@ def lib():
     L.sfs2d_plan_project.argtypes = [vp, i32, i32, vp, vp, i64, i64, vp, C.POINTER(i32)]
     L.sfs2d_plan_project_read.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.sfs2d_project_weights.argtypes = [i32, i32, i32, vp]
+    L.sfs2d_plan_project_scan.argtypes = [vp, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.sfs2d_plan_project_scan_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sfs2d_data_synth_sims.argtypes = [vp, C.POINTER(SynthParams), vp, vp, i32, vp, i32, C.POINTER(vp)]
     L.sfs2d_data_read.argtypes = [vp, vp, vp, i64]
     L.sfs2d_ctx_use_own_stream.argtypes = [vp]

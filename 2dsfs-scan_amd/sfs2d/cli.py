@@ -53,6 +53,14 @@ over the bins its subsamples fall in.  The file stems gain ``_proj<M1>x<M2>``, t
 ``(M1 + 1) x (M2 + 1)`` bins (foreground and background alike, folded unless ``--no-fold``; a tie of the joint fold
 stays where it is, dadi averages ties), the npz gains ``n_used`` and ``n_dropped`` and its 1D spectra are the grid's
 marginals; each output prints the share of its SNPs that the projection dropped.
+
+``--project-scan M1,M2`` scans every window again at the common sample size M1 / M2 (projected_scan; DESIGN.md
+section 19): T2D and T1D from the window's projected spectrum against its chromosome's, without the pull toward the
+low bins that missing calls give a window.  One more file per ``--window`` / ``--snp-window`` / sliding /
+``--regions`` output, ``<stem>_projscan<M1>x<M2>.csv``: ``chromosome, window_start, window_end`` (``name`` first for
+regions), ``snp_count, n_used, n_dropped, T2D_proj, T1D_pop1_proj, T1D_pop2_proj, new_term_pop1_proj,
+new_term_pop2_proj, T2D_diff_proj``; each prints the share of its SNPs that the projection dropped.  Every other
+file is what it is without the flag.
 """
 from __future__ import annotations
 
@@ -156,15 +164,36 @@ def parse_outlier_spec(text):
     return key, q
 
 
-def parse_project(text, n1p: int, n2p: int):
+def parse_project(text, n1p: int, n2p: int, flag: str = "--project"):
     """``M1,M2`` -> (M1, M2); ValueError with the reason for a malformed or out-of-range one."""
     try:
         m1, m2 = (int(x) for x in str(text).split(","))
     except ValueError:
-        raise ValueError(f"--project {text!r}: expected M1,M2 (two integers)") from None
+        raise ValueError(f"{flag} {text!r}: expected M1,M2 (two integers)") from None
     if not (2 <= m1 <= 2 * n1p and 2 <= m2 <= 2 * n2p):
-        raise ValueError(f"--project {text!r}: need 2 <= M1 <= {2 * n1p} and 2 <= M2 <= {2 * n2p}")
+        raise ValueError(f"{flag} {text!r}: need 2 <= M1 <= {2 * n1p} and 2 <= M2 <= {2 * n2p}")
     return m1, m2
+
+
+def write_projscan_csv(path, rows, chr_ids, regions=None):
+    """``<stem>_projscan<M1>x<M2>.csv``: the rows of projected_scan (sfs2d.spectra.PROJSCAN_COLUMNS) behind the
+    window's chromosome, start and end, with a leading ``name`` column for ``regions`` (one row per region in the
+    caller's order).  A None is an empty field."""
+    from .spectra import PROJSCAN_COLUMNS
+    head = ["chromosome", "window_start", "window_end"]
+    with open(path, "w", newline="") as fh:
+        w = csv.DictWriter(fh, fieldnames=(["name"] if regions is not None else []) + head + PROJSCAN_COLUMNS)
+        w.writeheader()
+        if regions is not None:
+            for key, s in zip(regions.keys(), regions.slot.tolist()):
+                chrom = regions.chrom_names[int(regions.chrom[s])]
+                w.writerow({"name": key, "chromosome": chr_ids.get(chrom, chrom), "window_start": int(regions.first[s]),
+                            "window_end": int(regions.last[s]), **rows[key]})
+            return
+        for label, r in rows.items():
+            chrom = label.split(" ")[0]
+            s, e = label.split(" ")[1].split("-")
+            w.writerow({"chromosome": chr_ids.get(chrom, chrom), "window_start": s, "window_end": e, **r})
 
 
 def _dropped_share(used, dropped) -> str:
@@ -226,6 +255,9 @@ def main(argv=None):
     ap.add_argument("--project", default=None, metavar="M1,M2",
                     help="with --outlier-spectra / --region-spectra: project the spectra down to M1 / M2 haploid "
                          "samples (SNPs with fewer called alleles are dropped); stems gain _proj<M1>x<M2>")
+    ap.add_argument("--project-scan", default=None, metavar="M1,M2",
+                    help="T2D / T1D of every window at the common sample size M1 / M2 (projected spectra against the "
+                         "projected chromosome) -> one <stem>_projscan<M1>x<M2>.csv per window output")
     ap.add_argument("--out-prefix", default="stats")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="VCF parser threads (0 = all)")
@@ -253,6 +285,12 @@ def main(argv=None):
         except ValueError as e:
             ap.error(str(e))
         ptag = "_proj{}x{}".format(*pkw["project"])
+    pscan = None
+    if a.project_scan is not None:
+        try:
+            pscan = parse_project(a.project_scan, a.pop1_size, a.pop2_size, "--project-scan")
+        except ValueError as e:
+            ap.error(str(e))
     null = a.null_replicates is not None
     block = None
     if a.null_block is not None:
@@ -299,6 +337,17 @@ def main(argv=None):
         rg = Regions.from_bed(packed, a.regions)
         rkw = dict(regions=rg)
 
+    def projscan_out(stem, **geometry):
+        # (the new flag alone: a scan of its own per file, nothing of the calls above changes)
+        if pscan is None:
+            return
+        rows = obj.projected_scan(packed, pscan, **geometry)
+        path = "{}_projscan{}x{}.csv".format(stem, *pscan)
+        write_projscan_csv(path, rows, chr_ids, geometry.get("regions"))
+        outs.append(path)
+        used, dropped = (sum(r[k] for r in rows.values()) for k in ("n_used", "n_dropped"))
+        print(f"projected_scan {pscan}: {len(rows)} windows, {_dropped_share(used, dropped)} -> {path}", file=sys.stderr)
+
     def regions_out(res):
         if rg is None:
             return
@@ -306,6 +355,7 @@ def main(argv=None):
         write_regions_csv(path, res["regions"], rg, chr_ids, a.fst, null, a.diversity)
         outs.append(path)
         print(f"region_scan: {len(rg)} regions -> {path}", file=sys.stderr)
+        projscan_out(f"{a.out_prefix}_regions", regions=rg)
 
     def spectra_out(size, **geometry):
         # (the new flags alone: a scan of its own per file, nothing of the calls above changes)
@@ -350,6 +400,7 @@ def main(argv=None):
             outs.append(path)
             print(f"sliding_scan {ws} bp / {a.step} bp: {len(rows)} windows -> {path}", file=sys.stderr)
             spectra_out(f"{_fmt_kb(ws)}_step{_fmt_kb(a.step)}", window_size=ws, step_size=a.step)
+            projscan_out(path[:-4], window_size=ws, step_size=a.step)
         regions_out(res)
         region_spectra_out()
         return outs
@@ -366,6 +417,7 @@ def main(argv=None):
         outs.append(path)
         print(f"combined_scan {ws} bp: {len(res[ws])} windows -> {path}", file=sys.stderr)
         spectra_out(_fmt_kb(ws), window_size=ws)
+        projscan_out(path[:-4], window_size=ws)
     for S in a.snp_window:
         stats = res[f"{S}snps"]
         fst = obj.window_fst(packed, snp_window_size=S) if a.fst else None
@@ -374,6 +426,7 @@ def main(argv=None):
         outs.append(path)
         print(f"scan_perChr_bySNPs {S} SNPs: {len(stats)} windows -> {path}", file=sys.stderr)
         spectra_out(f"{S}snps", snp_window_size=S)
+        projscan_out(path[:-4], snp_window_size=S)
     regions_out(res)
     region_spectra_out()
     return outs

@@ -430,6 +430,29 @@ class Plan:
                                                             C.byref(n), C.byref(w)))
         return out, used, dropped
 
+    def project_scan(self, m1: int, m2: int, bg_chrom: Optional[int] = None,
+                     out_dev_ptr: Optional[int] = None) -> Optional[np.ndarray]:
+        """T2D, T1D_pop1 and T1D_pop2 of every record of this plan's last run at the common haploid sample size
+        ``(m1, m2)`` (sfs2d_plan_project_scan): one PROJSTAT_DTYPE record per window record,
+        at the same index, each window's projected spectrum against its chromosome's (``bg_chrom`` None) or
+        against chromosome index ``bg_chrom``'s for every record.  NaN: an empty foreground or background; +inf: a
+        touched bin the background lacks.  ``self.project_scan_e`` / ``self.project_scan_e_bg`` hold the fixed
+        points of the window and background grids; two calls give equal arrays.  Any plan that has run with
+        per-chromosome backgrounds, attached plans included.  With ``out_dev_ptr`` (a device buffer of ``nrec``
+        records) nothing is copied to the host and None is returned."""
+        e, eb = C.c_int32(), C.c_int32()
+        self.eng.check(self.eng.lib.sfs2d_plan_project_scan(self.h, int(m1), int(m2), -1 if bg_chrom is None else int(bg_chrom),
+                                                            C.c_void_p(out_dev_ptr) if out_dev_ptr else None,
+                                                            C.byref(e), C.byref(eb)))
+        self.project_scan_e, self.project_scan_e_bg = e.value, eb.value
+        if out_dev_ptr:
+            return None
+        out = np.zeros(self.nrec, dtype=L.PROJSTAT_DTYPE)
+        n = C.c_int64()
+        self.eng.check(self.eng.lib.sfs2d_plan_project_scan_read(self.h, L.ptr(out) if self.nrec else None, self.nrec,
+                                                                 C.byref(n)))
+        return out
+
     def bg_buffer(self):
         p = C.c_void_p()
         nb = C.c_int64()

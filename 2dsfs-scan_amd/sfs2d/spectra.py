@@ -28,6 +28,14 @@ added to (m1 - j1, m2 - j2); a tie stays where it is, as the scan's fold leaves 
 the two halves of a tie instead), the two 1D marginals (``projected_marginals``) and their folds
 (``fold1d_projected``).  ``project_np`` is the exact twin (rational weights), the definition the tests compare
 against.
+
+The projected scan (k_proj_scan, csrc/sfs2d_projscan.hpp; ``Plan.project_scan``): T2D and T1D
+of EVERY window at the common sample size, each window's projected grid (folded when the plan folds) against its
+chromosome's.  With ``x = X.ravel()[1:-1]``, ``N = sum x``, ``B = sum b[1:-1]``: ``T2D = 2 sum_{x_k > 0} x_k (ln(x_k /
+N) - ln(b_k / B))`` = ``pooled_t2d(residuals(X, b))``, +inf when a touched bin has b_k = 0, NaN exactly when N = 0 or
+B = 0; T1D the same form on the folded marginal at its inner bins 1 <= j, 2 j < m_k.  The closed form is the
+statistic: the reference's exact 0.0 for proportional spectra and scipy's NaN rule for an empty last bin are not
+reproduced.  ``project_scan_np`` is the twin (tests only), ``project_scan_rows`` makes the result rows.
 """
 from __future__ import annotations
 
@@ -41,7 +49,7 @@ from .diversity import _filter_mask
 
 __all__ = ["split_row", "window_spectra_np", "select_top", "residuals", "pooled_t2d", "write_dadi_fs",
            "read_dadi_fs", "RESIDUAL_COLUMNS", "project_weights_exact", "project_np", "fold_projected",
-           "projected_marginals", "fold1d_projected"]
+           "projected_marginals", "fold1d_projected", "project_scan_np", "project_scan_rows", "PROJSCAN_COLUMNS"]
 
 RESIDUAL_COLUMNS = ["x1", "x2", "fg_count", "bg_count", "fg_p", "bg_p", "diff", "t2d_term"]
 
@@ -252,6 +260,92 @@ def fold1d_projected(sfs1d):
     for j in range(m // 2 + 1):
         out[..., j] = x[..., j] if j == m - j else x[..., j] + x[..., m - j]
     return out
+
+
+def _llr(x, b):
+    """2 sum_{x_k > 0} x_k (ln(x_k / N) - ln(b_k / B)) of two equally long sequences of floats or Fractions, and N:
+    NaN when N = 0 or B = 0, +inf when a bin with x_k > 0 has b_k = 0."""
+    exact = len(x) > 0 and isinstance(x[0], Fraction)
+    N, B = (sum(x), sum(b)) if exact else (math.fsum(x), math.fsum(b))
+    if N == 0 or B == 0:
+        return math.nan, N
+    terms = []
+    for xk, bk in zip(x, b):
+        if xk > 0:
+            if bk == 0:
+                return math.inf, N
+            terms.append(float(xk) * (math.log(xk / N) - math.log(bk / B)))
+    return 2.0 * math.fsum(terms), N
+
+
+def project_scan_np(p, recs, cfg, m1: int, m2: int, bg_chrom=None, exact: bool = False):
+    """The twin of ``Plan.project_scan`` (tests only): a structured array, one entry per record, of ``t2d``,
+    ``t1d_p1``, ``t1d_p2`` (float64), ``n2``, ``n1a``, ``n1b`` (the three N, float64), ``n_used``, ``n_dropped``
+    and ``flags``, from ``project_np``'s grids of the records and of the chromosomes (``bg_chrom`` None: each record
+    against its own chromosome; else chromosome index ``bg_chrom`` for every record), ``fold_projected`` when
+    ``cfg.fold``, ``projected_marginals`` and ``fold1d_projected``.  ``exact``: the sums and ratios in rationals,
+    one logarithm per ratio; else in float64 from the correctly rounded grids."""
+    m1, m2 = int(m1), int(m2)
+    nrec = len(recs)
+    if bg_chrom is not None and not 0 <= int(bg_chrom) < p.nchrom:
+        raise ValueError(f"project_scan: bg_chrom {bg_chrom} outside [0, {p.nchrom})")
+    chroms = list(range(p.nchrom)) if bg_chrom is None else [int(bg_chrom)]
+    rec = list(range(nrec)) + [-(c + 1) for c in chroms]
+    grids, used, dropped = project_np(p, recs, cfg, m1, m2, rec, np.arange(len(rec)), len(rec), exact=exact)
+    if cfg.fold:
+        grids = fold_projected(grids)
+    s1, s2 = projected_marginals(grids)
+    f1, f2 = fold1d_projected(s1), fold1d_projected(s2)
+    in1 = [j for j in range(1, m1 + 1) if 2 * j < m1]
+    in2 = [j for j in range(1, m2 + 1) if 2 * j < m2]
+    flat = grids.reshape(len(rec), -1)
+    out = np.zeros(nrec, np.dtype([("t2d", "<f8"), ("t1d_p1", "<f8"), ("t1d_p2", "<f8"), ("n2", "<f8"), ("n1a", "<f8"),
+                                   ("n1b", "<f8"), ("n_used", "<i8"), ("n_dropped", "<i8"), ("flags", "<u4")]))
+    for i in range(nrec):
+        fl = int(recs[i]["flags"]) & (L.W_EMPTY | L.W_EXTRA)
+        if fl:
+            out[i]["flags"] = fl
+            continue
+        g = nrec + (0 if bg_chrom is not None else int(recs[i]["chrom"]))
+        t2, n2 = _llr(flat[i][1:-1].tolist(), flat[g][1:-1].tolist())
+        ta, na = _llr([f1[i][j] for j in in1], [f1[g][j] for j in in1])
+        tb, nb = _llr([f2[i][j] for j in in2], [f2[g][j] for j in in2])
+        out[i] = (t2, ta, tb, float(n2), float(na), float(nb), int(used[i]), int(dropped[i]), 0)
+    return out
+
+
+PROJSCAN_COLUMNS = ["snp_count", "n_used", "n_dropped", "T2D_proj", "T1D_pop1_proj", "T1D_pop2_proj",
+                    "new_term_pop1_proj", "new_term_pop2_proj", "T2D_diff_proj"]
+
+
+def project_scan_rows(recs, stats, labels) -> dict:
+    """{label: PROJSCAN_COLUMNS} of the labelled records of a projected scan: ``recs`` the plan's window records,
+    ``stats`` ``Plan.project_scan``'s (or the twin's) at the same indices, ``labels`` one per record (None: a
+    record that is no window of its own, left out).  A NaN statistic (an empty foreground or background) is None,
+    +inf stays, a labelled record that is no window (an empty region) has None throughout; the differences follow the scans' clean None rules -- None when a statistic they read is None, and
+    also where both are +inf (the difference is undefined)."""
+    def val(v):
+        v = float(v)
+        return None if math.isnan(v) else v
+
+    def diff(a, *b):
+        if a is None or any(x is None for x in b):
+            return None
+        d = a - math.fsum(b) / len(b)
+        return None if math.isnan(d) else d
+    rows = {}
+    for r, s, lb in zip(recs, stats, labels):
+        if lb is None:
+            continue
+        if int(s["flags"]) & (L.W_EMPTY | L.W_EXTRA):   # (a region without SNPs: a row of its own, nothing to report)
+            T2D = T1 = T2 = None
+        else:
+            T2D, T1, T2 = val(s["t2d"]), val(s["t1d_p1"]), val(s["t1d_p2"])
+        rows[lb] = {"snp_count": int(r["snp_count"]), "n_used": int(s["n_used"]), "n_dropped": int(s["n_dropped"]),
+                    "T2D_proj": T2D, "T1D_pop1_proj": T1, "T1D_pop2_proj": T2,
+                    "new_term_pop1_proj": diff(T2D, T1), "new_term_pop2_proj": diff(T2D, T2),
+                    "T2D_diff_proj": diff(T2D, T1, T2)}
+    return rows
 
 
 def select_top(rows: dict, key: str, q: float):

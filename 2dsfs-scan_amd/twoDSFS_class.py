@@ -980,6 +980,52 @@ class LikelihoodInference_jointSFS:
         return {"labels": top, "foreground": g.copy(), "sfs1d_pop1": f1.copy(), "sfs1d_pop2": f2.copy(),
                 "background": bg_grid, "background_chromosomes": bg_names, "residuals": res, "T2D": SP.pooled_t2d(res)}
 
+    # ------------------------------------------------------------------ projected scan (extension)
+    def projected_scan(self, data_dict, project, window_size=None, snp_window_size=None, step_size=None, regions=None,
+                       background_chromosome=None):
+        """T2D and T1D of every window at a common sample size: the scan's statistics from spectra projected down
+        hypergeometrically to ``project`` = (m1, m2) haploid samples, each window against its chromosome projected
+        the same way (``background_chromosome``: that chromosome for every window, as scan_chooseChr).  The scans
+        bin a SNP by its raw alt count whatever its called count, so a window where calls are missing -- low
+        coverage, repeats, one population sequenced worse -- has its spectrum pushed toward the low bins and T2D
+        reports that as signal; here only SNPs called in at least m_k alleles of both populations count, each
+        spread over the bins its subsamples fall in (k_proj_scan, on the GPU).  Windows as in
+        ``window_spectra``: ``window_size`` (with ``step_size`` sliding), ``snp_window_size`` or ``regions``, labels
+        as the corresponding scans emit them.  Returns {label: {snp_count, n_used, n_dropped, T2D_proj,
+        T1D_pop1_proj, T1D_pop2_proj, new_term_pop1_proj, new_term_pop2_proj, T2D_diff_proj}}
+        (sfs2d.spectra.project_scan_rows): None for an empty foreground or background, +inf where the window
+        touches a bin its background lacks.  The statistic is the closed form 2 sum x_k (ln(x_k / N) - ln(b_k /
+        B)) over the inner bins; the reference's exact 0.0 for proportional spectra is not reproduced.  The
+        reference has no projection."""
+        self._no_distributed_spectra("projected_scan")
+        project = self._check_project(project)
+        p = self._pack(data_dict)
+        bg_chrom = None
+        if background_chromosome is not None:
+            if background_chromosome not in p.chrom_names:
+                raise ValueError(f"Background chromosome {background_chromosome} not found in the data.")
+            bg_chrom = p.chrom_names.index(background_chromosome)
+        cfg, kind, w, step, rg = self._spectra_cfg(p, window_size, snp_window_size, step_size, regions,
+                                                   bg_mode=L.BG_PER_CHROM)
+        from sfs2d import spectra as SP
+        eng = self._engine()
+        dev = eng.upload(p)
+        try:
+            pl = eng.plan(dev, cfg)
+            try:
+                pl.run()
+                pl.check()
+                recs = pl.read()
+                stats = pl.project_scan(*project, bg_chrom)
+            finally:
+                pl.close()
+        finally:
+            dev.close()
+        if rg is not None:   # (one row per region, in the caller's order)
+            order = rg.slot.tolist()
+            return SP.project_scan_rows(recs[order], stats[order], list(rg.keys()))
+        return SP.project_scan_rows(recs, stats, post.record_labels(recs, p, kind, w, step))
+
     # ------------------------------------------------------------------ SFS primitives
     def calculate_2d_sfs(self, data_dict):
         """2D SFS dict over the grid (140-232), accumulated on the GPU (distributed: every rank a slice

@@ -42,7 +42,7 @@ extern "C" {
  * an argument); sfs2d_plan_diversity / _diversity_read and sfs2d_diversity added (additive);
  * sfs2d_plan_create_regions / sfs2d_plan_attach_regions added (additive: the intervals are arguments);
  * sfs2d_plan_spectra / _spectra_read added (additive); sfs2d_plan_project / _project_read and
- * sfs2d_project_weights added (additive) */
+ * sfs2d_project_weights added (additive); sfs2d_plan_project_scan / _project_scan_read added (additive) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -461,6 +461,53 @@ int sfs2d_plan_project_read(sfs2d_plan* plan, double* out_host, int64_t* used, i
  * kernel evaluates (ln k! table, one exp per weight; exactly 0 outside the support, exactly 1 on a support of one
  * bin).  SFS2D_E_ARG: a > n, m > n, n > 510, a negative argument or w_out == NULL */
 int sfs2d_project_weights(int32_t n, int32_t a, int32_t m, double* w_out);
+/* The projected scan: T2D, T1D_pop1 and T1D_pop2 of EVERY record of the plan's last run at the
+ * common haploid sample size (m1, m2), 2 <= m_k <= 2 pop_size_k -- the scan's statistics without the pull toward the
+ * low bins that missing calls give a window (the scan bins a SNP by its raw alt count whatever its called count).  One
+ * record per record of the last run, at the same index.  Members, used and dropped SNPs, the weights and the fixed
+ * point are sfs2d_plan_project's; per record:
+ *   window grid X  the projected (m1 + 1) x (m2 + 1) grid of its SNP range [begin, end) (clamped to the data set),
+ *                  folded jointly when the plan folds: bin (j1, j2) with 2 (j1 + j2) > m1 + m2 is added to
+ *                  (m1 - j1, m2 - j2), a tie stays where it is; unfolded otherwise
+ *   background b   the same grid over the whole chromosome the record's chrom names, under the same membership
+ *                  (bg_chrom = -1), or over chromosome bg_chrom for every record (bg_chrom >= 0)
+ *   t2d            2 sum_{x_k > 0} x_k (ln(x_k / N) - ln(b_k / B)), x = X.ravel()[1:-1], N = sum x, B = sum b[1:-1];
+ *                  +inf when a touched bin has b_k = 0; NaN exactly when N = 0 or B = 0
+ *   t1d_p1/_p2     the same form on the marginal of the grid folded min(j, m_k - j), at its inner bins 1 <= j,
+ *                  2 j < m_k (bin 0 and, for even m_k, the bin at m_k / 2 are not read: at m_k = 2 pop_size_k these
+ *                  are the bins 1 .. pop_size_k - 1 that T1D reads), against the chromosome's marginal
+ *   n2_fx, n1a_fx, n1b_fx  the three N as integers at the fixed point 2^-e; n_used / n_dropped as sfs2d_plan_project
+ *   flags          SFS2D_W_EMPTY / SFS2D_W_EXTRA of the source record; such a record has every other field 0
+ * The statistic is the closed form above: the reference's exact 0.0 for proportional spectra and scipy's NaN rule for
+ * an empty last bin are not reproduced (on fully called data at m_k = 2 pop_size_k it agrees with the scan's T to
+ * rounding wherever that is finite and non-zero).  Every term of a grid is rounded to nearest once and the sums are
+ * integer; the floating-point sums run in a fixed order: two calls give byte-equal records, however the records fall
+ * to workgroups.  *e_out: the windows' fixed point, e = min(40, 62 - bitlen(the plan's bound on a window's SNPs)),
+ * what sfs2d_plan_project reports for one record per group; *e_bg_out: the backgrounds', by sfs2d_plan_project's rule
+ * for one chromosome entry per group (NULL: not wanted).  The window grids live in LDS alone (8 bytes per bin beside
+ * the marginals and a 4 KB table): there is no global-memory variant.
+ * out_dev: sfs2d_plan_num_records records on the device (NULL = plan-owned, read with sfs2d_plan_project_scan_read).
+ * Enqueued on the ctx stream after the plan's last run (sfs2d_plan_read's: a replay by sfs2d_graph_launch counts, a
+ * capture alone does not), nothing is read back; any plan that has run, attached, sliding, regions, SNP-count and
+ * filtered plans and wrapped device data included.  Reads the records, the counts and (filtered plans) the per-SNP
+ * bins, writes out_dev and its own buffers alone: a following run, null run, diversity, spectra or project call finds
+ * everything as it was, and sfs2d_plan_project_read still reads the last sfs2d_plan_project call.
+ * SFS2D_E_ARG, the reason in sfs2d_last_error: a plan that has not run, m_k < 2 or m_k > 2 pop_size_k, bg_chrom
+ * outside [-1, nchrom), a plan with a supplied background (SFS2D_BG_SUPPLIED); SFS2D_E_CAP: a grid that does not fit
+ * the 160 KB of LDS of a compute unit, fewer than 8 fraction bits; SFS2D_E_NOMEM.
+ * The reference has no projection and scans raw alt counts (twoDSFS_class.py:787-991). */
+typedef struct {
+  double t2d, t1d_p1, t1d_p2;
+  int64_t n2_fx, n1a_fx, n1b_fx;   /* N of T2D / T1D_pop1 / T1D_pop2, fixed point 2^-e */
+  uint32_t n_used, n_dropped;
+  uint32_t flags;                  /* SFS2D_W_EMPTY | SFS2D_W_EXTRA bits of the source record */
+  uint32_t e;
+} sfs2d_projstat;
+int sfs2d_plan_project_scan(sfs2d_plan* plan, int32_t m1, int32_t m2, int32_t bg_chrom, sfs2d_projstat* out_dev,
+                            int32_t* e_out, int32_t* e_bg_out);
+/* copy the last sfs2d_plan_project_scan call's records to host (synchronises); SFS2D_E_CAP: cap below the record
+ * count (*nrec_out holds it); SFS2D_E_ARG: no such call since the plan was created */
+int sfs2d_plan_project_scan_read(sfs2d_plan* plan, sfs2d_projstat* out_host, int64_t cap, int64_t* nrec_out);
 /* launch geometry (threads per grid) of k_prep and of the scan kernel: matches the Grid_Size column
  * of rocprofv3 kernel traces, so profiles can be joined to a plan */
 int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* scan_threads);
