@@ -160,6 +160,21 @@ struct sfs2d_data {
   mutable uint32_t* d_pidx_sh = nullptr;
 };
 
+// A grow-on-demand device array of a post-scan call (reserve) and a call's result (call_out, read_last): the
+// plan-owned buffer, where the last call wrote -- that buffer or the caller's -- and how many elements; NONE: no
+// call yet.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;   // elements
+};
+template <typename T, int64_t NONE = -1>
+struct CallOut {
+  DevBuf<T> own;
+  const T* last = nullptr;
+  int64_t n = NONE;
+};
+
 struct sfs2d_plan {
   sfs2d_ctx* ctx = nullptr;
   const sfs2d_data* data = nullptr;
@@ -250,52 +265,30 @@ struct sfs2d_plan {
   bool gate = false;              // Fst in the scan, folded, called counts within (n1, n2): k_scan_w's GATE variants
   bool lean = false;              // gate, fixed-bp slot records, n1p, n2p <= 31: k_scan_w's LEAN variants (same results)
   int nfst = 0;                   // k_bg_slice's extra Fst workgroups
-  // bootstrap null (sfs2d_plan_null_run): the last call's task table and records
+  // bootstrap null (sfs2d_plan_null_run): the last call's task table and records (a read before any call: 0 records)
   std::vector<NullTask> ntask_h;
-  NullTask* d_ntask = nullptr;
-  size_t ntask_cap = 0;
-  sfs2d_window* d_null = nullptr;        // plan-owned records (out_dev == NULL)
-  size_t null_cap = 0;
-  const sfs2d_window* null_last = nullptr;   // where the last call wrote (sfs2d_plan_null_read copies from it)
-  int64_t null_nrec = 0;
+  DevBuf<NullTask> ntask;
+  CallOut<sfs2d_window, 0> null_out;
   // template arguments of the scan kernel the last run launched (sfs2d_plan_scan_variant), written by
   // launch_scan from the selection it launches: {P16, FUSED, FST, CNT, GATE, TRI}, -1 where the kernel has none
   int variant[6] = {-1, -1, -1, -1, -1, -1};
   bool variant_set = false;
-  // diversity (sfs2d_plan_diversity): the plan-owned records and where the last call wrote
-  sfs2d_diversity* d_div = nullptr;
-  const sfs2d_diversity* div_last = nullptr;
-  int64_t div_nrec = -1;                 // records of the last call (-1: none yet)
-  // window spectra (sfs2d_plan_spectra): the last call's selection, the plan-owned rows and where the call wrote
-  std::vector<SpecSel> spec_sel_h;
-  SpecSel* d_spec_sel = nullptr;
-  size_t spec_sel_cap = 0;
-  int64_t* d_spec = nullptr;             // plan-owned rows (out_dev == NULL)
-  size_t spec_cap = 0;                   // ... in int64 words
-  const int64_t* spec_last = nullptr;
-  int64_t spec_words = -1;               // words of the last call (-1: none yet)
-  int spec_lds_ok = -1;                  // the row's LDS histogram: -1 not asked yet, 1 granted, 0 refused (global atomics)
-  // projected window spectra (sfs2d_plan_project): as the spectra's, and the last call's shape and fixed point
-  std::vector<ProjSel> proj_sel_h;
-  ProjSel* d_proj_sel = nullptr;
-  size_t proj_sel_cap = 0;
-  int64_t* d_proj = nullptr;             // plan-owned rows (out_dev == NULL)
-  size_t proj_cap = 0;                   // ... in int64 words
-  const int64_t* proj_last = nullptr;
-  int64_t proj_groups = -1, proj_roww = 0;   // groups and row words of the last call (-1: none yet)
+  // the other post-scan calls ("post-scan calls: the common skeleton"): the last call's selection on the
+  // host and the device, scratch arrays, and the call's result
+  CallOut<sfs2d_diversity> div_out;      // sfs2d_plan_diversity: records
+  std::vector<SpecSel> spec_sel_h;       // sfs2d_plan_spectra
+  DevBuf<SpecSel> spec_sel;
+  CallOut<int64_t> spec_out;             // ... int64 words
+  std::vector<ProjSel> proj_sel_h;       // sfs2d_plan_project
+  DevBuf<ProjSel> proj_sel;
+  CallOut<int64_t> proj_out;             // ... groups; its words are proj_out.n * proj_roww
+  int64_t proj_roww = 0;                 // row words of the last call
   int proj_e = 0;                        // its fixed point 2^-e
-  // the projected scan (sfs2d_plan_project_scan): the background chromosomes' selection, rows and ln tables, and
-  // the plan-owned records
-  std::vector<ProjSel> pscan_sel_h;
-  ProjSel* d_pscan_sel = nullptr;
-  size_t pscan_sel_cap = 0;
-  unsigned long long* d_pscan_bg = nullptr;
-  size_t pscan_bg_cap = 0;               // ... in words
-  double* d_pscan_lp = nullptr;
-  size_t pscan_lp_cap = 0;
-  sfs2d_projstat* d_pscan = nullptr;
-  const sfs2d_projstat* pscan_last = nullptr;
-  int64_t pscan_nrec = -1;               // records of the last call (-1: none yet)
+  std::vector<ProjSel> pscan_sel_h;      // sfs2d_plan_project_scan: the background chromosomes' selection,
+  DevBuf<ProjSel> pscan_sel;
+  DevBuf<unsigned long long> pscan_bg;   // their rows
+  DevBuf<double> pscan_lp;               // and ln tables
+  CallOut<sfs2d_projstat> pscan_out;     // records
   int64_t maxsnp = 0;                    // plan_create's bound on the SNPs of one record (Fst's e, P16)
   // runs enqueued for EXECUTION, apart from `runs` (the parity of the buffers the next enqueued run takes): a run
   // enqueued into a graph capture counts when the graph is launched (sfs2d_graph_launch), not at the capture.  The
@@ -348,10 +341,10 @@ void plan_free(sfs2d_plan* p) {
   hipFree(p->d_done); hipFree(p->d_bgval); hipFree(p->d_tab); hipFree(p->d_lp); hipFree(p->d_head);
   hipFree(p->d_bg1d); hipFree(p->d_leafsum); hipFree(p->d_leaves); hipFree(p->d_nodes); hipFree(p->d_slices);
   hipFree(p->d_out); hipFree(p->d_err); hipFree(p->d_bins); hipFree(p->d_fst_own); hipFree(p->d_fsum); hipFree(p->d_gscr);
-  hipFree(p->d_ntask); hipFree(p->d_null); hipFree(p->d_div);
-  hipFree(p->d_spec_sel); hipFree(p->d_spec);
-  hipFree(p->d_proj_sel); hipFree(p->d_proj);
-  hipFree(p->d_pscan_sel); hipFree(p->d_pscan_bg); hipFree(p->d_pscan_lp); hipFree(p->d_pscan);
+  hipFree(p->ntask.p); hipFree(p->null_out.own.p); hipFree(p->div_out.own.p);
+  hipFree(p->spec_sel.p); hipFree(p->spec_out.own.p);
+  hipFree(p->proj_sel.p); hipFree(p->proj_out.own.p);
+  hipFree(p->pscan_sel.p); hipFree(p->pscan_bg.p); hipFree(p->pscan_lp.p); hipFree(p->pscan_out.own.p);
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->tev) if (e) hipEventDestroy(e);
 }
@@ -362,6 +355,9 @@ int plan_par(const sfs2d_plan* pl) {
 }
 // replica parity: only fused plans alternate replicas (k_bg_slice clears what it reads)
 int repl_par(const sfs2d_plan* pl) { return pl->fused ? plan_par(pl) : 0; }
+
+// the records of the plan's last executed run: where that run wrote them (the caller's buffer or the plan's own)
+const sfs2d_window* last_records(const sfs2d_plan* pl) { return pl->last_out ? pl->last_out : pl->d_out; }
 
 // what the scan kernels stream per SNP: the bins k_prep wrote, or (counts plans) the counts themselves
 const uint32_t* scan_src(const sfs2d_plan* pl) { return pl->cnt ? pl->data->counts : pl->d_bins; }
@@ -493,7 +489,7 @@ typename S::Fn variant(sfs2d_ctx* ctx, S s, const char* family, int* rc) {
   return k;
 }
 
-// the dynamic-LDS limit on every instantiation of a family (the first error, if any)
+// the dynamic-LDS limit on every instantiation of a family (the first error, if any): grant_lds alone calls it
 template <class S>
 hipError_t set_max_lds(size_t lds) {
   hipError_t e = hipSuccess;
@@ -503,6 +499,26 @@ hipError_t set_max_lds(size_t lds) {
     if (e == hipSuccess) e = ek;
   }
   return e;
+}
+
+// The one place that raises a family's dynamic-LDS limit.  hipFuncSetAttribute sets the limit to exactly the size
+// asked for, on the device's copy of a kernel and for every plan that launches it, so the limit is kept per device
+// and family and only grows: a call that needs less than an earlier one leaves it alone.  Returns whether the
+// family may launch with `lds` bytes of dynamic LDS (a refusal clears the HIP error: the callers fall back or
+// refuse in their own words).
+std::mutex lds_mu;
+template <class S>
+bool grant_lds(sfs2d_ctx* ctx, size_t lds) {
+  static std::map<int, size_t> granted;   // device -> the dynamic LDS the family's instantiations may take
+  std::lock_guard<std::mutex> lk(lds_mu);
+  size_t& have = granted[ctx->device];
+  if (lds <= have) return true;
+  if (set_max_lds<S>(lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  have = lds;
+  return true;
 }
 
 // a selection's static LDS (fallback: the query failed) and its resident workgroups per CU (0: it failed)
@@ -1425,7 +1441,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
         const ScanGW gs = occ_standin(scan_gw_sel(pl));
         auto gw_occ = [&](size_t lds) {
           if (lds > 160 * 1024) return 0;
-          if (lds > 64 * 1024) set_max_lds<ScanGW>(lds);
+          if (lds > 64 * 1024) grant_lds<ScanGW>(ctx, lds);
           return occupancy(gs, WAVE, lds);
         };
         occ = gw_occ(gw_lds);
@@ -1514,10 +1530,10 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   if (env.slots_once) pl->slots_once = pl->slots_once && env.slots_once[0] != '0';
   pl->nfst = pl->fst_win && !slide ? (int)std::min<int64_t>(1024, std::max<int64_t>(1, (pl->nslots + 7) / 8)) : 0;   // ~1 window per wave
   if (pl->scan_lds > 64 * 1024) {   // (k_scan_gw's: with its occupancy, above)
-    set_max_lds<ScanW>(pl->scan_lds);
-    set_max_lds<ScanG>(pl->scan_lds);
+    grant_lds<ScanW>(ctx, pl->scan_lds);
+    grant_lds<ScanG>(ctx, pl->scan_lds);
   }
-  if (pl->extra_lds > 64 * 1024) set_max_lds<ScanExtra>(pl->extra_lds);
+  if (pl->extra_lds > 64 * 1024) grant_lds<ScanExtra>(ctx, pl->extra_lds);
 
   // scan work items.  k_scan_w: about one workgroup per resident slot (one dispatch wave, no
   // tail), shared among the chromosomes by window count; each wavefront takes one static window,
@@ -1636,10 +1652,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
     }
   }
   // the large dynamic LDS refused: the global-atomic histogram instead
-  if (pl->lds_hist && pl->bg_lds > 64 * 1024 && set_max_lds<Prep>(pl->bg_lds) != hipSuccess) {
-    (void)hipGetLastError();
-    pl->lds_hist = false;
-  }
+  if (pl->lds_hist && pl->bg_lds > 64 * 1024 && !grant_lds<Prep>(ctx, pl->bg_lds)) pl->lds_hist = false;
   hipFuncSetAttribute((const void*)k_bg_finalize, hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)(sizeof(double) * FIN_LDS_BINS));
 
@@ -2245,12 +2258,136 @@ int sfs2d_plan_read(sfs2d_plan* pl, sfs2d_window* out_host, int64_t cap, int64_t
                                      "is launched)");
   if (cap < pl->nrec) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
   if (pl->nrec && !out_host) return SFS2D_E_ARG;
-  const sfs2d_window* src = pl->last_out ? pl->last_out : pl->d_out;
   if (pl->nrec)
-    HIPCHK(ctx, hipMemcpyAsync(out_host, src, sizeof(sfs2d_window) * pl->nrec, hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
+    HIPCHK(ctx, hipMemcpyAsync(out_host, last_records(pl), sizeof(sfs2d_window) * pl->nrec, hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
   HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------ post-scan calls
+// The calls below work on the records of a plan's last executed run and share one skeleton ("post-scan
+// calls: the common skeleton"): post_ready -- the plan has run, 32-bit SNP indices, the device, the last run's
+// records; the selection (sel_shape, sel_rows_fit, sel_walk); device arrays that grow on demand (reserve) and the
+// call's result in the caller's buffer or the plan's own (call_out); the LDS grant (grant_lds); the launch; and
+// the read of what the last call wrote (read_ready, read_last).
+
+extern "C++" {
+namespace {
+
+// What a post-scan call needs before it looks at its own arguments: the plan has run (a run that was only captured
+// has not executed: sfs2d_graph_launch counts it), SNP indices fit 32 bits and the device is current.  *recs: the
+// last run's records.  unrun: the call's own words for a plan that has not run (the null's).
+int post_ready(sfs2d_plan* pl, const char* name, const sfs2d_window** recs, const char* unrun = nullptr) {
+  sfs2d_ctx* ctx = pl->ctx;
+  if (pl->done == 0)
+    return set_err(ctx, SFS2D_E_ARG,
+                   unrun ? std::string(unrun)
+                         : std::string(name) + (pl->base ? " before the base plan's first run (an attached plan has no records yet)"
+                                                         : " before the plan's first run (no records yet)"));
+  if (pl->data->n > 0xffffffffll)
+    return set_err(ctx, SFS2D_E_ARG, std::string(name) + ": data set too large for 32-bit SNP indices");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  *recs = last_records(pl);
+  return 0;
+}
+
+// The shape of a selection (rec, grp, nsel, ngroups) of sfs2d_plan_spectra and sfs2d_plan_project ...
+int sel_shape(sfs2d_plan* pl, const std::string& name, const int64_t* rec, const int32_t* grp, int64_t nsel,
+              int64_t ngroups) {
+  sfs2d_ctx* ctx = pl->ctx;
+  if (nsel < 0) return set_err(ctx, SFS2D_E_ARG, name + ": nsel must be >= 0");
+  if (ngroups < 1) return set_err(ctx, SFS2D_E_ARG, name + ": ngroups must be >= 1");
+  if (!rec && nsel != pl->nrec)
+    return set_err(ctx, SFS2D_E_ARG, name + ": rec == NULL selects every record in order: nsel must be the plan's record count");
+  if (rec && !grp) return set_err(ctx, SFS2D_E_ARG, name + ": grp == NULL needs rec == NULL (group i = record i)");
+  if (nsel > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, name + ": more than 2^32 - 1 selection entries");
+  if (!grp && nsel > ngroups)
+    return set_err(ctx, SFS2D_E_ARG, name + ": group i = record i needs ngroups >= the plan's record count");
+  return 0;
+}
+// ... its rows, ngroups x roww int64 words, in 64 bits (the two calls ask at different points: spectra after the
+// entries, project before them, so an argument set with two faults is refused for the same one as ever) ...
+int sel_rows_fit(sfs2d_plan* pl, const std::string& name, int64_t ngroups, int64_t roww) {
+  if (ngroups > 0xffffffffll || ngroups > (INT64_MAX / 8) / roww)
+    return set_err(pl->ctx, SFS2D_E_NOMEM, name + ": " + std::to_string(ngroups) + " rows of " + std::to_string(roww) +
+                                               " int64 words do not fit");
+  return 0;
+}
+// ... and its entries: entry(i, r, g) for entry i of record r in [0, nrec) and group g in [0, ngroups), its return
+// value other than 0 ending the walk.  neg: a negative r is the callback's to judge (project's chromosome
+// entries); such a call names a bad group before a bad record, the other a bad record first.
+template <class Entry>
+int sel_walk(sfs2d_plan* pl, const std::string& name, const int64_t* rec, const int32_t* grp, int64_t nsel,
+             int64_t ngroups, bool neg, Entry entry) {
+  sfs2d_ctx* ctx = pl->ctx;
+  for (int64_t i = 0; i < nsel; ++i) {
+    const int64_t r = rec ? rec[i] : i, g = grp ? (int64_t)grp[i] : i;
+    const bool bad_r = r >= pl->nrec || (r < 0 && !neg), bad_g = g < 0 || g >= ngroups;
+    if (bad_g && (neg || !bad_r))
+      return set_err(ctx, SFS2D_E_ARG, name + ": entry " + std::to_string(i) + ": group " + std::to_string(g) +
+                                           " outside [0, " + std::to_string(ngroups) + ")");
+    if (bad_r)
+      return set_err(ctx, SFS2D_E_ARG, name + ": entry " + std::to_string(i) + ": record " + std::to_string(r) +
+                                           " outside [0, " + std::to_string(pl->nrec) + ")");
+    const int rc = entry(i, r, g);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// b holds `want` elements: what it held is replaced when it is too small -- after the stream has been synchronised,
+// once per call (*synced), since an earlier call may still read what is replaced.  A failed allocation leaves b
+// empty and the HIP error cleared.
+template <typename T>
+int reserve(sfs2d_ctx* ctx, hipStream_t st, DevBuf<T>& b, size_t want, bool* synced) {
+  if (want <= b.cap) return 0;
+  if (b.p && !*synced) {
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    *synced = true;
+  }
+  hipFree(b.p);
+  b.cap = 0;
+  const int rc = dalloc(ctx, &b.p, want);
+  if (rc) (void)hipGetLastError();
+  else b.cap = want;
+  return rc;
+}
+// *out: where a call writes its n elements -- the caller's buffer, or the plan's own, which grows to hold them (the
+// earlier result is then gone: no call yet)
+template <typename T, int64_t NONE>
+int call_out(sfs2d_ctx* ctx, hipStream_t st, CallOut<T, NONE>& o, T* out_dev, size_t n, bool* synced, T** out) {
+  if (!out_dev && n > o.own.cap) {
+    o.last = nullptr;
+    o.n = NONE;
+    const int rc = reserve(ctx, st, o.own, n, synced);
+    if (rc) return rc;
+  }
+  *out = out_dev ? out_dev : o.own.p;
+  return 0;
+}
+
+// the refusals of a read call -- no call yet, a capacity below the count, which *n_out reports either way -- ...
+template <typename T, int64_t NONE>
+int read_ready(sfs2d_plan* pl, const CallOut<T, NONE>& o, int64_t cap, int64_t* n_out, const char* name) {
+  if (o.n < 0) return set_err(pl->ctx, SFS2D_E_ARG, std::string(name) + "_read before " + name);
+  *n_out = o.n;
+  if (cap < o.n) return set_err(pl->ctx, SFS2D_E_CAP, "output capacity too small");
+  return 0;
+}
+// ... and the read itself: the elements the last call wrote, from where it wrote them (synchronises)
+template <typename T, int64_t NONE>
+int read_last(sfs2d_plan* pl, const CallOut<T, NONE>& o, T* host, int64_t cap, int64_t* n_out, const char* name) {
+  sfs2d_ctx* ctx = pl->ctx;
+  const int rc = read_ready(pl, o, cap, n_out, name);
+  if (rc) return rc;
+  if (o.n && !host) return SFS2D_E_ARG;
+  if (o.n) HIPCHK(ctx, hipMemcpyAsync(host, o.last, sizeof(T) * (size_t)o.n, hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
+  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
+  return 0;
+}
+
+}  // namespace
+}  // extern "C++"
 
 // ------------------------------------------------------------------------------------------ bootstrap null
 
@@ -2308,11 +2445,11 @@ int launch_null(sfs2d_plan* pl, uint32_t R, unsigned long long nrec, uint2 key, 
   const unsigned long long want = (nrec + wpb - 1) / wpb;
   const unsigned grid = (unsigned)std::min<unsigned long long>(want, (unsigned long long)occ * ctx->ncu);
   if (block == 1u)
-    hipLaunchKernelGGL((k_null<P16, CNT>), dim3(grid), dim3(wpb * WAVE), lds, CTX_STREAM(ctx), K, scan_src(pl), pl->d_ntask, R,
+    hipLaunchKernelGGL((k_null<P16, CNT>), dim3(grid), dim3(wpb * WAVE), lds, CTX_STREAM(ctx), K, scan_src(pl), pl->ntask.p, R,
                        nrec, key, pl->d_tab, pl->d_head, pl->do_bg ? 1 : 0, ctx->d_lnx, out);
   else
     hipLaunchKernelGGL((k_null_blk<P16, CNT>), dim3(grid), dim3(wpb * WAVE), lds, CTX_STREAM(ctx), K, scan_src(pl),
-                       pl->d_ntask, R, nrec, key, block, pl->d_tab, pl->d_head, pl->do_bg ? 1 : 0, ctx->d_lnx, out);
+                       pl->ntask.p, R, nrec, key, block, pl->d_tab, pl->d_head, pl->do_bg ? 1 : 0, ctx->d_lnx, out);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
@@ -2334,11 +2471,11 @@ int sfs2d_plan_null_run_blocks(sfs2d_plan* pl, const sfs2d_null_params* np, int6
   if (block < 1 || block > 0xffffffffll)
     return set_err(ctx, SFS2D_E_ARG, "null run: block length " + std::to_string(block) + " must be in [1, 2^32)");
   if (pl->base) return set_err(ctx, SFS2D_E_ARG, "null run on an attached plan: use its base plan (same data, same tables)");
-  if (pl->done == 0)
-    return set_err(ctx, SFS2D_E_ARG, "null run before the plan's first run (no background tables yet; a captured run counts "
-                                     "once its graph is launched)");
+  const sfs2d_window* recs = nullptr;   // (not read: the null draws from the pools and the run's tables)
+  int rc = post_ready(pl, "null run", &recs, "null run before the plan's first run (no background tables yet; a captured run "
+                                             "counts once its graph is launched)");
+  if (rc) return rc;
   if (np->replicates < 1) return set_err(ctx, SFS2D_E_ARG, "null run: replicates must be >= 1");
-  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "null run: data set too large for 32-bit SNP indices");
   pl->ntask_h.resize((size_t)ntasks);
   uint32_t maxm = 0;
   for (int64_t t = 0; t < ntasks; ++t) {
@@ -2356,34 +2493,16 @@ int sfs2d_plan_null_run_blocks(sfs2d_plan* pl, const sfs2d_null_params* np, int6
   }
   const unsigned long long nrec = (unsigned long long)ntasks * np->replicates;
   if (nrec > (1ull << 26)) return set_err(ctx, SFS2D_E_CAP, "null run: more than 2^26 records in one call (split the tasks)");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = CTX_STREAM(ctx);
-  if ((size_t)ntasks > pl->ntask_cap || (!out_dev && nrec > pl->null_cap)) {
-    HIPCHK(ctx, hipStreamSynchronize(st));   // an earlier call may still read what is replaced
-    if ((size_t)ntasks > pl->ntask_cap) {
-      hipFree(pl->d_ntask);
-      pl->ntask_cap = 0;
-      int rc = dalloc(ctx, &pl->d_ntask, (size_t)ntasks);
-      if (rc) return rc;
-      pl->ntask_cap = (size_t)ntasks;
-    }
-    if (!out_dev && nrec > pl->null_cap) {
-      hipFree(pl->d_null);
-      pl->null_cap = 0;
-      pl->null_last = nullptr;
-      pl->null_nrec = 0;
-      int rc = dalloc(ctx, &pl->d_null, (size_t)nrec);
-      if (rc) return rc;
-      pl->null_cap = (size_t)nrec;
-    }
-  }
-  sfs2d_window* out = out_dev ? out_dev : pl->d_null;
-  pl->null_last = out;
-  pl->null_nrec = (int64_t)nrec;
+  bool synced = false;
+  sfs2d_window* out = nullptr;
+  if ((rc = reserve(ctx, st, pl->ntask, (size_t)ntasks, &synced))) return rc;
+  if ((rc = call_out(ctx, st, pl->null_out, out_dev, (size_t)nrec, &synced, &out))) return rc;
+  pl->null_out.last = out;
+  pl->null_out.n = (int64_t)nrec;
   if (nrec == 0) return 0;
-  int rc = null_tables(pl);
-  if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(pl->d_ntask, pl->ntask_h.data(), sizeof(NullTask) * (size_t)ntasks, hipMemcpyHostToDevice, st));
+  if ((rc = null_tables(pl))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(pl->ntask.p, pl->ntask_h.data(), sizeof(NullTask) * (size_t)ntasks, hipMemcpyHostToDevice, st));
   const uint2 key = make_uint2((uint32_t)np->seed, (uint32_t)(np->seed >> 32));
   // u16-packed 2D bins while no bin can hold 65536 draws
   const uint32_t blk = (uint32_t)block;
@@ -2396,15 +2515,7 @@ int sfs2d_plan_null_run_blocks(sfs2d_plan* pl, const sfs2d_null_params* np, int6
 
 int sfs2d_plan_null_read(sfs2d_plan* pl, sfs2d_window* out_host, int64_t cap, int64_t* nrec_out) {
   if (!pl || !nrec_out) return SFS2D_E_ARG;
-  sfs2d_ctx* ctx = pl->ctx;
-  *nrec_out = pl->null_nrec;
-  if (cap < pl->null_nrec) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
-  if (pl->null_nrec && !out_host) return SFS2D_E_ARG;
-  if (pl->null_nrec)
-    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->null_last, sizeof(sfs2d_window) * (size_t)pl->null_nrec, hipMemcpyDeviceToHost,
-                               CTX_STREAM(ctx)));
-  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
-  return 0;
+  return read_last(pl, pl->null_out, out_host, cap, nrec_out, "sfs2d_plan_null");
 }
 
 // ------------------------------------------------------------------------------------------ diversity
@@ -2413,20 +2524,15 @@ int sfs2d_plan_diversity(sfs2d_plan* pl, sfs2d_diversity* out_dev) {
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   const sfs2d_data* d = pl->data;
-  if (pl->done == 0)   // (a run that was only captured has not executed: sfs2d_graph_launch counts it)
-    return set_err(ctx, SFS2D_E_ARG, pl->base ? "diversity before the base plan's first run (an attached plan has no records yet)"
-                                              : "diversity before the plan's first run (no records yet)");
-  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "diversity: data set too large for 32-bit SNP indices");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!out_dev && !pl->d_div && pl->nrec) {
-    int rc = dalloc(ctx, &pl->d_div, (size_t)pl->nrec);
-    if (rc) return rc;
-  }
-  sfs2d_diversity* out = out_dev ? out_dev : pl->d_div;
-  pl->div_last = out;
-  pl->div_nrec = pl->nrec;
+  const sfs2d_window* recs = nullptr;
+  int rc = post_ready(pl, "diversity", &recs);
+  if (rc) return rc;
+  bool synced = false;
+  sfs2d_diversity* out = nullptr;
+  if ((rc = call_out(ctx, CTX_STREAM(ctx), pl->div_out, out_dev, (size_t)pl->nrec, &synced, &out))) return rc;
+  pl->div_out.last = out;
+  pl->div_out.n = pl->nrec;
   if (pl->nrec == 0) return 0;
-  const sfs2d_window* recs = pl->last_out ? pl->last_out : pl->d_out;
   // one wavefront per record, four per workgroup, the records strided over at most 2048 workgroups (as k_fst_win)
   const uint32_t nrec = (uint32_t)pl->nrec;
   const dim3 g((unsigned)std::min<uint32_t>(2048u, (nrec + 3u) / 4u));
@@ -2443,16 +2549,7 @@ int sfs2d_plan_diversity(sfs2d_plan* pl, sfs2d_diversity* out_dev) {
 
 int sfs2d_plan_diversity_read(sfs2d_plan* pl, sfs2d_diversity* out_host, int64_t cap, int64_t* nrec_out) {
   if (!pl || !nrec_out) return SFS2D_E_ARG;
-  sfs2d_ctx* ctx = pl->ctx;
-  if (pl->div_nrec < 0) return set_err(ctx, SFS2D_E_ARG, "sfs2d_plan_diversity_read before sfs2d_plan_diversity");
-  *nrec_out = pl->div_nrec;
-  if (cap < pl->div_nrec) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
-  if (pl->div_nrec && !out_host) return SFS2D_E_ARG;
-  if (pl->div_nrec)
-    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->div_last, sizeof(sfs2d_diversity) * (size_t)pl->div_nrec, hipMemcpyDeviceToHost,
-                               CTX_STREAM(ctx)));
-  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
-  return 0;
+  return read_last(pl, pl->div_out, out_host, cap, nrec_out, "sfs2d_plan_diversity");
 }
 
 // ------------------------------------------------------------------------------------------ window spectra
@@ -2462,79 +2559,36 @@ int sfs2d_plan_spectra(sfs2d_plan* pl, const int64_t* rec, const int32_t* grp, i
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   const sfs2d_data* d = pl->data;
-  if (pl->done == 0)   // (a run that was only captured has not executed: sfs2d_graph_launch counts it)
-    return set_err(ctx, SFS2D_E_ARG, pl->base ? "spectra before the base plan's first run (an attached plan has no records yet)"
-                                              : "spectra before the plan's first run (no records yet)");
-  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "spectra: data set too large for 32-bit SNP indices");
-  if (nsel < 0) return set_err(ctx, SFS2D_E_ARG, "spectra: nsel must be >= 0");
-  if (ngroups < 1) return set_err(ctx, SFS2D_E_ARG, "spectra: ngroups must be >= 1");
-  if (!rec && nsel != pl->nrec)
-    return set_err(ctx, SFS2D_E_ARG, "spectra: rec == NULL selects every record in order: nsel must be the plan's record count");
-  if (rec && !grp) return set_err(ctx, SFS2D_E_ARG, "spectra: grp == NULL needs rec == NULL (group i = record i)");
-  if (nsel > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "spectra: more than 2^32 - 1 selection entries");
-  if (!grp && nsel > ngroups)
-    return set_err(ctx, SFS2D_E_ARG, "spectra: group i = record i needs ngroups >= the plan's record count");
+  const sfs2d_window* recs = nullptr;
+  int rc = post_ready(pl, "spectra", &recs);
+  if (rc || (rc = sel_shape(pl, "spectra", rec, grp, nsel, ngroups))) return rc;
   pl->spec_sel_h.resize((size_t)nsel);
   int64_t nruns = 0, prev_g = -1;   // maximal runs of consecutive entries of one group
-  for (int64_t i = 0; i < nsel; ++i) {
-    const int64_t r = rec ? rec[i] : i, g = grp ? (int64_t)grp[i] : i;
-    if (r < 0 || r >= pl->nrec)
-      return set_err(ctx, SFS2D_E_ARG, "spectra: entry " + std::to_string(i) + ": record " + std::to_string(r) +
-                                           " outside [0, " + std::to_string(pl->nrec) + ")");
-    if (g < 0 || g >= ngroups)
-      return set_err(ctx, SFS2D_E_ARG, "spectra: entry " + std::to_string(i) + ": group " + std::to_string(g) +
-                                           " outside [0, " + std::to_string(ngroups) + ")");
+  rc = sel_walk(pl, "spectra", rec, grp, nsel, ngroups, false, [&](int64_t i, int64_t r, int64_t g) {
     pl->spec_sel_h[(size_t)i] = SpecSel{(uint32_t)r, (uint32_t)g};
     nruns += g != prev_g;
     prev_g = g;
-  }
+    return 0;
+  });
+  if (rc) return rc;
   // groups x row in 64 bits: the row is at most 255 x 255 + 256 words
   const int64_t roww = (int64_t)pl->K.nb2 + pl->K.n1p + pl->K.n2p + 2;
-  if (ngroups > 0xffffffffll || ngroups > (INT64_MAX / 8) / roww)
-    return set_err(ctx, SFS2D_E_NOMEM, "spectra: " + std::to_string(ngroups) + " rows of " + std::to_string(roww) +
-                                           " int64 words do not fit");
+  if ((rc = sel_rows_fit(pl, "spectra", ngroups, roww))) return rc;
   const int64_t words = ngroups * roww;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = CTX_STREAM(ctx);
-  if ((size_t)nsel > pl->spec_sel_cap || (!out_dev && (size_t)words > pl->spec_cap)) {
-    HIPCHK(ctx, hipStreamSynchronize(st));   // an earlier call may still read what is replaced
-    if ((size_t)nsel > pl->spec_sel_cap) {
-      hipFree(pl->d_spec_sel);
-      pl->spec_sel_cap = 0;
-      int rc = dalloc(ctx, &pl->d_spec_sel, (size_t)nsel);
-      if (rc) return rc;
-      pl->spec_sel_cap = (size_t)nsel;
-    }
-    if (!out_dev && (size_t)words > pl->spec_cap) {
-      hipFree(pl->d_spec);
-      pl->spec_cap = 0;
-      pl->spec_words = -1;
-      int rc = dalloc(ctx, &pl->d_spec, (size_t)words);
-      if (rc) {
-        (void)hipGetLastError();
-        return rc;
-      }
-      pl->spec_cap = (size_t)words;
-    }
-  }
-  int64_t* out = out_dev ? out_dev : pl->d_spec;
-  // the row's u32 histogram in LDS while a CU can hold it; above the default limit the kernels opt in, once per
-  // plan, and a refusal selects the global-atomic instantiations (as k_prep's histogram)
+  bool synced = false;
+  int64_t* out = nullptr;
+  if ((rc = reserve(ctx, st, pl->spec_sel, (size_t)nsel, &synced))) return rc;
+  if ((rc = call_out(ctx, st, pl->spec_out, out_dev, (size_t)words, &synced, &out))) return rc;
+  // the row's u32 histogram in LDS while a CU can hold it; above the default limit the family opts in, and a
+  // refusal selects the global-atomic instantiations (as k_prep's histogram)
   const size_t lds = sizeof(uint32_t) * (size_t)roww;
-  if (pl->spec_lds_ok < 0) {
-    pl->spec_lds_ok = lds <= 160 * 1024 ? 1 : 0;
-    if (pl->spec_lds_ok && lds > 64 * 1024 && set_max_lds<SpecWin>(lds) != hipSuccess) {
-      (void)hipGetLastError();
-      pl->spec_lds_ok = 0;
-    }
-  }
-  const bool ldsh = pl->spec_lds_ok == 1;
+  const bool ldsh = lds <= 160 * 1024 && (lds <= 64 * 1024 || grant_lds<SpecWin>(ctx, lds));
   HIPCHK(ctx, hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)words, st));
-  pl->spec_last = out;
-  pl->spec_words = words;
+  pl->spec_out.last = out;
+  pl->spec_out.n = words;
   if (nsel == 0) return 0;
-  HIPCHK(ctx, hipMemcpyAsync(pl->d_spec_sel, pl->spec_sel_h.data(), sizeof(SpecSel) * (size_t)nsel, hipMemcpyHostToDevice, st));
-  int rc = 0;
+  HIPCHK(ctx, hipMemcpyAsync(pl->spec_sel.p, pl->spec_sel_h.data(), sizeof(SpecSel) * (size_t)nsel, hipMemcpyHostToDevice, st));
   const SpecWin::Fn k = variant(ctx, SpecWin{pl->cnt, ldsh}, "k_spec_win", &rc);
   if (!k) return rc;
   // A contiguous run of the selection per workgroup, at most as many workgroups as are resident with the row in
@@ -2546,8 +2600,7 @@ int sfs2d_plan_spectra(sfs2d_plan* pl, const int64_t* rec, const int32_t* grp, i
   const int per_cu = ldsh ? (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / lds)) : 8;
   const int64_t want = std::max<int64_t>(std::max<int64_t>(ctx->ncu, nruns), nsel / 4);
   const dim3 g((unsigned)std::min<int64_t>(nsel, std::min<int64_t>(want, (int64_t)per_cu * ctx->ncu)));
-  const sfs2d_window* recs = pl->last_out ? pl->last_out : pl->d_out;
-  hipLaunchKernelGGL(k, g, dim3(SPEC_BLOCK), ldsh ? lds : 0, st, pl->K, d->counts, scan_src(pl), recs, pl->d_spec_sel,
+  hipLaunchKernelGGL(k, g, dim3(SPEC_BLOCK), ldsh ? lds : 0, st, pl->K, d->counts, scan_src(pl), recs, pl->spec_sel.p,
                      reinterpret_cast<unsigned long long*>(out), (uint32_t)nsel, (uint32_t)pl->nrec, (uint32_t)ngroups,
                      (uint32_t)d->n);
   HIPCHK(ctx, hipGetLastError());
@@ -2556,16 +2609,7 @@ int sfs2d_plan_spectra(sfs2d_plan* pl, const int64_t* rec, const int32_t* grp, i
 
 int sfs2d_plan_spectra_read(sfs2d_plan* pl, int64_t* out_host, int64_t cap_words, int64_t* nwords_out) {
   if (!pl || !nwords_out) return SFS2D_E_ARG;
-  sfs2d_ctx* ctx = pl->ctx;
-  if (pl->spec_words < 0) return set_err(ctx, SFS2D_E_ARG, "sfs2d_plan_spectra_read before sfs2d_plan_spectra");
-  *nwords_out = pl->spec_words;
-  if (cap_words < pl->spec_words) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
-  if (pl->spec_words && !out_host) return SFS2D_E_ARG;
-  if (pl->spec_words)
-    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->spec_last, sizeof(int64_t) * (size_t)pl->spec_words, hipMemcpyDeviceToHost,
-                               CTX_STREAM(ctx)));
-  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
-  return 0;
+  return read_last(pl, pl->spec_out, out_host, cap_words, nwords_out, "sfs2d_plan_spectra");
 }
 
 // ------------------------------------------------------------------------------------------ projected window spectra
@@ -2595,26 +2639,55 @@ int sfs2d_project_weights(int32_t n, int32_t a, int32_t m, double* w_out) {
 }
 
 namespace {
-// k_proj_win's row histogram in LDS: whether `lds` bytes of it fit a CU beside the table of ln k!, opting the
-// family in above the default limit (a refusal selects the global-atomic instantiations)
-bool proj_win_ldsh(sfs2d_ctx* ctx, size_t lds) {
-  bool ldsh = lds + 4096 <= 160 * 1024;
-  if (ldsh && lds > 64 * 1024) {
-    static std::mutex mu;
-    static std::map<int, size_t> granted;   // device -> the dynamic LDS its k_proj_win instantiations may take
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& have = granted[ctx->device];
-    if (lds > have) {
-      if (set_max_lds<ProjWin>(lds) != hipSuccess) {
-        (void)hipGetLastError();
-        ldsh = false;
-      } else {
-        have = lds;
-      }
-    }
-  }
-  return ldsh;
+
+// the table of ln k! on the device, uploaded by the first call that projects
+int proj_tables(sfs2d_ctx* ctx) {
+  if (ctx->d_lf) return 0;
+  const int rc = dalloc(ctx, &ctx->d_lf, (size_t)PROJ_LF);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpy(ctx->d_lf, proj_lf_table(), sizeof(double) * PROJ_LF, hipMemcpyHostToDevice));
+  return 0;
 }
+
+// the fixed point 2^-e of a grid that receives B SNPs at most: e = min(40, 62 - bitlen(B))
+int proj_fixed_point(unsigned __int128 B) {
+  int b = 0;
+  while (b < 64 && (B >> b) != 0) ++b;
+  return std::min(40, 62 - b);
+}
+
+// k_proj_win over nsel selection entries into ngroups rows at the fixed point 2^-e (the rows zeroed by the caller)
+int launch_proj_win(sfs2d_plan* pl, const sfs2d_window* recs, const ProjSel* sel, size_t nsel, unsigned long long* rows,
+                    uint32_t ngroups, int32_t m1, int32_t m2, int e) {
+  sfs2d_ctx* ctx = pl->ctx;
+  // the row's u64 histogram in LDS while a CU can hold it beside the 4 KB table of ln k!; above the default limit
+  // the family opts in, and a refusal selects the global-atomic instantiations
+  const size_t lds = sizeof(unsigned long long) * ((size_t)(m1 + 1) * (size_t)(m2 + 1) + 2);
+  const bool ldsh = lds + 4096 <= 160 * 1024 && (lds <= 64 * 1024 || grant_lds<ProjWin>(ctx, lds));
+  int rc = 0;
+  const ProjWin::Fn k = variant(ctx, ProjWin{pl->cnt, ldsh}, "k_proj_win", &rc);
+  if (!k) return rc;
+  // A contiguous run of the selection per workgroup, as many workgroups as are resident with the row in LDS (one
+  // entry each at most).  Unlike k_spec_win the kernel is bound by its fp64 weights, not by the flushes: one
+  // chromosome entry at (40, 40) of 50 took 790 us from 256 workgroups of 4,096-SNP pieces (DESIGN.md section 18).
+  const int per_cu = ldsh ? (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds + 4096))) : 8;
+  const dim3 g((unsigned)std::min<int64_t>((int64_t)nsel, (int64_t)per_cu * ctx->ncu));
+  hipLaunchKernelGGL(k, g, dim3(PROJ_BLOCK), ldsh ? lds : 0, CTX_STREAM(ctx), pl->K, pl->data->counts, scan_src(pl), recs, sel,
+                     ctx->d_lf, rows, (uint32_t)nsel, (uint32_t)pl->nrec, ngroups, (uint32_t)pl->data->n, (uint32_t)m1,
+                     (uint32_t)m2, std::ldexp(1.0, e), 1ull << (62 - e));
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+// one chromosome as selection entries of group g: pieces of PROJ_CHUNK SNPs, consecutive entries of one group (a
+// chromosome is streamed by many workgroups, where a record's range is known on the device alone); returns its SNPs
+int64_t push_chrom(std::vector<ProjSel>& sel, const sfs2d_data* d, int64_t c, uint32_t g) {
+  const int64_t cb = d->chrom_off[(size_t)c], ce = d->chrom_off[(size_t)c + 1];
+  for (int64_t s = cb; s < ce; s += PROJ_CHUNK)
+    sel.push_back(ProjSel{0xffffffffu, g, (uint32_t)s, (uint32_t)std::min<int64_t>(s + PROJ_CHUNK, ce)});
+  return ce - cb;
+}
+
 }  // namespace
 
 int sfs2d_plan_project(sfs2d_plan* pl, int32_t m1, int32_t m2, const int64_t* rec, const int32_t* grp, int64_t nsel,
@@ -2622,53 +2695,32 @@ int sfs2d_plan_project(sfs2d_plan* pl, int32_t m1, int32_t m2, const int64_t* re
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   const sfs2d_data* d = pl->data;
-  if (pl->done == 0)   // (a run that was only captured has not executed: sfs2d_graph_launch counts it)
-    return set_err(ctx, SFS2D_E_ARG, pl->base ? "project before the base plan's first run (an attached plan has no records yet)"
-                                              : "project before the plan's first run (no records yet)");
+  const sfs2d_window* recs = nullptr;
+  int rc = post_ready(pl, "project", &recs);
+  if (rc) return rc;
   if (m1 < 2 || m1 > pl->K.n1 || m2 < 2 || m2 > pl->K.n2)
     return set_err(ctx, SFS2D_E_ARG, "project: (m1, m2) = (" + std::to_string(m1) + ", " + std::to_string(m2) +
                                          ") outside [2, " + std::to_string(pl->K.n1) + "] x [2, " + std::to_string(pl->K.n2) + "]");
-  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project: data set too large for 32-bit SNP indices");
-  if (nsel < 0) return set_err(ctx, SFS2D_E_ARG, "project: nsel must be >= 0");
-  if (ngroups < 1) return set_err(ctx, SFS2D_E_ARG, "project: ngroups must be >= 1");
-  if (!rec && nsel != pl->nrec)
-    return set_err(ctx, SFS2D_E_ARG, "project: rec == NULL selects every record in order: nsel must be the plan's record count");
-  if (rec && !grp) return set_err(ctx, SFS2D_E_ARG, "project: grp == NULL needs rec == NULL (group i = record i)");
-  if (nsel > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project: more than 2^32 - 1 selection entries");
-  if (!grp && nsel > ngroups)
-    return set_err(ctx, SFS2D_E_ARG, "project: group i = record i needs ngroups >= the plan's record count");
   const int64_t roww = (int64_t)(m1 + 1) * (m2 + 1) + 2;   // at most 255 x 255 + 2 words
-  if (ngroups > 0xffffffffll || ngroups > (INT64_MAX / 8) / roww)
-    return set_err(ctx, SFS2D_E_NOMEM, "project: " + std::to_string(ngroups) + " rows of " + std::to_string(roww) +
-                                           " int64 words do not fit");
+  if ((rc = sel_shape(pl, "project", rec, grp, nsel, ngroups)) || (rc = sel_rows_fit(pl, "project", ngroups, roww))) return rc;
   pl->proj_sel_h.clear();
   pl->proj_sel_h.reserve((size_t)nsel);
   // B: the SNPs one group can receive -- its entries times the bound on one entry's SNPs (a record's: plan_create's
   // maxsnp; with chromosome entries in the selection, the longest chromosome, which is no smaller)
   int64_t per_entry = std::max<int64_t>(1, pl->maxsnp);
-  for (int64_t i = 0; i < nsel; ++i) {
-    const int64_t r = rec ? rec[i] : i, g = grp ? (int64_t)grp[i] : i;
-    if (g < 0 || g >= ngroups)
-      return set_err(ctx, SFS2D_E_ARG, "project: entry " + std::to_string(i) + ": group " + std::to_string(g) +
-                                           " outside [0, " + std::to_string(ngroups) + ")");
-    if (r < 0) {   // -(c + 1): the whole chromosome c
-      const int64_t c = -(r + 1);
-      if (c >= d->nchrom)
-        return set_err(ctx, SFS2D_E_ARG, "project: entry " + std::to_string(i) + ": chromosome " + std::to_string(c) +
-                                             " outside [0, " + std::to_string(d->nchrom) + ")");
-      // (in pieces of PROJ_CHUNK SNPs, consecutive entries of one group: a chromosome is streamed by many
-      // workgroups, where a record's range is known on the device alone)
-      const int64_t cb = d->chrom_off[(size_t)c], ce = d->chrom_off[(size_t)c + 1];
-      for (int64_t s = cb; s < ce; s += PROJ_CHUNK)
-        pl->proj_sel_h.push_back(ProjSel{0xffffffffu, (uint32_t)g, (uint32_t)s, (uint32_t)std::min<int64_t>(s + PROJ_CHUNK, ce)});
-      per_entry = std::max<int64_t>(per_entry, ce - cb);
-    } else {
-      if (r >= pl->nrec)
-        return set_err(ctx, SFS2D_E_ARG, "project: entry " + std::to_string(i) + ": record " + std::to_string(r) +
-                                             " outside [0, " + std::to_string(pl->nrec) + ")");
+  rc = sel_walk(pl, "project", rec, grp, nsel, ngroups, true, [&](int64_t i, int64_t r, int64_t g) {
+    if (r >= 0) {
       pl->proj_sel_h.push_back(ProjSel{(uint32_t)r, (uint32_t)g, 0u, 0u});
+      return 0;
     }
-  }
+    const int64_t c = -(r + 1);   // -(c + 1): the whole chromosome c
+    if (c >= d->nchrom)
+      return set_err(ctx, SFS2D_E_ARG, "project: entry " + std::to_string(i) + ": chromosome " + std::to_string(c) +
+                                           " outside [0, " + std::to_string(d->nchrom) + ")");
+    per_entry = std::max<int64_t>(per_entry, push_chrom(pl->proj_sel_h, d, c, (uint32_t)g));
+    return 0;
+  });
+  if (rc) return rc;
   int64_t maxent = nsel ? 1 : 0;   // the most entries of one group (grp == NULL: one each)
   if (grp) {
     std::vector<int32_t> gs(grp, grp + nsel);
@@ -2678,95 +2730,47 @@ int sfs2d_plan_project(sfs2d_plan* pl, int32_t m1, int32_t m2, const int64_t* re
       maxent = std::max(maxent, run);
     }
   }
-  int e;
-  {
-    const unsigned __int128 B = (unsigned __int128)std::max<int64_t>(1, maxent) * (unsigned __int128)per_entry;
-    int b = 0;
-    while (b < 64 && (B >> b) != 0) ++b;   // bit length of B
-    e = std::min(40, 62 - b);
-    if (e < 8)
-      return set_err(ctx, SFS2D_E_CAP, "project: " + std::to_string(maxent) + " entries of up to " + std::to_string(per_entry) +
-                                           " SNPs in one group leave fewer than 8 fraction bits in 64-bit sums");
-  }
+  const int e = proj_fixed_point((unsigned __int128)std::max<int64_t>(1, maxent) * (unsigned __int128)per_entry);
+  if (e < 8)
+    return set_err(ctx, SFS2D_E_CAP, "project: " + std::to_string(maxent) + " entries of up to " + std::to_string(per_entry) +
+                                         " SNPs in one group leave fewer than 8 fraction bits in 64-bit sums");
   if (e_out) *e_out = e;
   nsel = (int64_t)pl->proj_sel_h.size();   // (from here on: the entries the kernel walks)
   if (nsel > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project: more than 2^32 - 1 selection entries");
   const int64_t words = ngroups * roww;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = CTX_STREAM(ctx);
-  if (!ctx->d_lf) {
-    int rc = dalloc(ctx, &ctx->d_lf, (size_t)PROJ_LF);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy(ctx->d_lf, proj_lf_table(), sizeof(double) * PROJ_LF, hipMemcpyHostToDevice));
-  }
-  if ((size_t)nsel > pl->proj_sel_cap || (!out_dev && (size_t)words > pl->proj_cap)) {
-    HIPCHK(ctx, hipStreamSynchronize(st));   // an earlier call may still read what is replaced
-    if ((size_t)nsel > pl->proj_sel_cap) {
-      hipFree(pl->d_proj_sel);
-      pl->proj_sel_cap = 0;
-      int rc = dalloc(ctx, &pl->d_proj_sel, (size_t)nsel);
-      if (rc) return rc;
-      pl->proj_sel_cap = (size_t)nsel;
-    }
-    if (!out_dev && (size_t)words > pl->proj_cap) {
-      hipFree(pl->d_proj);
-      pl->proj_cap = 0;
-      pl->proj_groups = -1;
-      int rc = dalloc(ctx, &pl->d_proj, (size_t)words);
-      if (rc) {
-        (void)hipGetLastError();
-        return rc;
-      }
-      pl->proj_cap = (size_t)words;
-    }
-  }
-  int64_t* out = out_dev ? out_dev : pl->d_proj;
-  // the row's u64 histogram in LDS while a CU can hold it beside the 4 KB table of ln k!; above the default limit
-  // the kernels opt in, and a refusal selects the global-atomic instantiations.  The projection changes from call to
-  // call and the limit belongs to the kernels, not to a plan: per device it only grows.
-  const size_t lds = sizeof(unsigned long long) * (size_t)roww;
-  const bool ldsh = proj_win_ldsh(ctx, lds);
+  if ((rc = proj_tables(ctx))) return rc;
+  bool synced = false;
+  int64_t* out = nullptr;
+  if ((rc = reserve(ctx, st, pl->proj_sel, (size_t)nsel, &synced))) return rc;
+  if ((rc = call_out(ctx, st, pl->proj_out, out_dev, (size_t)words, &synced, &out))) return rc;   // (words; n: groups)
   HIPCHK(ctx, hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)words, st));
-  pl->proj_last = out;
-  pl->proj_groups = ngroups;
+  pl->proj_out.last = out;
+  pl->proj_out.n = ngroups;
   pl->proj_roww = roww;
   pl->proj_e = e;
   if (nsel == 0) return 0;
-  HIPCHK(ctx, hipMemcpyAsync(pl->d_proj_sel, pl->proj_sel_h.data(), sizeof(ProjSel) * (size_t)nsel, hipMemcpyHostToDevice, st));
-  int rc = 0;
-  const ProjWin::Fn k = variant(ctx, ProjWin{pl->cnt, ldsh}, "k_proj_win", &rc);
-  if (!k) return rc;
-  // A contiguous run of the selection per workgroup, as many workgroups as are resident with the row in LDS (one
-  // entry each at most).  Unlike k_spec_win the kernel is bound by its fp64 weights, not by the flushes: one
-  // chromosome entry at (40, 40) of 50 took 790 us from 256 workgroups of 4,096-SNP pieces (DESIGN.md section 18).
-  const int per_cu = ldsh ? (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds + 4096))) : 8;
-  const dim3 g((unsigned)std::min<int64_t>(nsel, (int64_t)per_cu * ctx->ncu));
-  const sfs2d_window* recs = pl->last_out ? pl->last_out : pl->d_out;
-  hipLaunchKernelGGL(k, g, dim3(PROJ_BLOCK), ldsh ? lds : 0, st, pl->K, d->counts, scan_src(pl), recs, pl->d_proj_sel,
-                     ctx->d_lf, reinterpret_cast<unsigned long long*>(out), (uint32_t)nsel, (uint32_t)pl->nrec,
-                     (uint32_t)ngroups, (uint32_t)d->n, (uint32_t)m1, (uint32_t)m2, std::ldexp(1.0, e),
-                     1ull << (62 - e));
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
+  HIPCHK(ctx, hipMemcpyAsync(pl->proj_sel.p, pl->proj_sel_h.data(), sizeof(ProjSel) * (size_t)nsel, hipMemcpyHostToDevice, st));
+  return launch_proj_win(pl, recs, pl->proj_sel.p, (size_t)nsel, reinterpret_cast<unsigned long long*>(out), (uint32_t)ngroups,
+                         m1, m2, e);
 }
 
 int sfs2d_plan_project_read(sfs2d_plan* pl, double* out_host, int64_t* used, int64_t* dropped, int64_t cap_groups,
                             int64_t* ngroups_out, int64_t* words_per_group) {
   if (!pl || !ngroups_out || !words_per_group) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
-  if (pl->proj_groups < 0) return set_err(ctx, SFS2D_E_ARG, "sfs2d_plan_project_read before sfs2d_plan_project");
-  *ngroups_out = pl->proj_groups;
-  *words_per_group = pl->proj_roww - 2;
-  if (cap_groups < pl->proj_groups) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
+  if (pl->proj_out.n >= 0) *words_per_group = pl->proj_roww - 2;
+  const int rc = read_ready(pl, pl->proj_out, cap_groups, ngroups_out, "sfs2d_plan_project");
+  if (rc) return rc;
   if (!out_host || !used || !dropped) return SFS2D_E_ARG;
-  const size_t roww = (size_t)pl->proj_roww, ngrid = roww - 2, ng = (size_t)pl->proj_groups;
+  const size_t roww = (size_t)pl->proj_roww, ngrid = roww - 2, ng = (size_t)pl->proj_out.n;
   std::vector<int64_t> raw;
   try {
     raw.resize(ng * roww);
   } catch (const std::bad_alloc&) {
     return set_err(ctx, SFS2D_E_NOMEM, "project_read: host staging buffer");
   }
-  HIPCHK(ctx, hipMemcpyAsync(raw.data(), pl->proj_last, sizeof(int64_t) * raw.size(), hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
+  HIPCHK(ctx, hipMemcpyAsync(raw.data(), pl->proj_out.last, sizeof(int64_t) * raw.size(), hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
   HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
   const double inv = std::ldexp(1.0, -pl->proj_e);
   for (size_t g = 0; g < ng; ++g) {
@@ -2785,9 +2789,9 @@ int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_c
   if (!pl) return SFS2D_E_ARG;
   sfs2d_ctx* ctx = pl->ctx;
   const sfs2d_data* d = pl->data;
-  if (pl->done == 0)   // (a run that was only captured has not executed: sfs2d_graph_launch counts it)
-    return set_err(ctx, SFS2D_E_ARG, pl->base ? "project_scan before the base plan's first run (an attached plan has no records yet)"
-                                              : "project_scan before the plan's first run (no records yet)");
+  const sfs2d_window* recs = nullptr;
+  int rc = post_ready(pl, "project_scan", &recs);
+  if (rc) return rc;
   if (pl->prm.bg_mode == SFS2D_BG_SUPPLIED)
     return set_err(ctx, SFS2D_E_ARG, "project_scan: a plan with a supplied background has no projected background "
                                      "(only per-chromosome plans; bg_chrom names one chromosome for every record)");
@@ -2797,7 +2801,6 @@ int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_c
   if (bg_chrom < -1 || bg_chrom >= d->nchrom)
     return set_err(ctx, SFS2D_E_ARG, "project_scan: bg_chrom " + std::to_string(bg_chrom) + " outside [-1, " +
                                          std::to_string(d->nchrom) + ")");
-  if (d->n > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project_scan: data set too large for 32-bit SNP indices");
   if (pl->nrec > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project_scan: more than 2^32 - 1 records");
   const int64_t ngrid = (int64_t)(m1 + 1) * (m2 + 1), roww = ngrid + 2, lpw = ngrid + (m1 + 1) + (m2 + 1);
   // the window grid, its marginals and sums in LDS beside the 4 KB table: there is no global-memory variant (a
@@ -2807,24 +2810,14 @@ int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_c
     return set_err(ctx, SFS2D_E_CAP, "project_scan: the (" + std::to_string(m1 + 1) + " x " + std::to_string(m2 + 1) +
                                          ") window grid takes " + std::to_string(lds + 4096) +
                                          " bytes of LDS, more than the 163840 of a compute unit");
-  auto fixed_point = [](int64_t B) {   // e = min(40, 62 - bitlen(B))
-    int b = 0;
-    while (b < 63 && (B >> b) != 0) ++b;
-    return std::min(40, 62 - b);
-  };
   // windows: one record per grid; backgrounds: one chromosome entry per row (section 18's rule for such a call)
   const int64_t per_rec = std::max<int64_t>(1, pl->maxsnp);
   const int nbg = bg_chrom < 0 ? d->nchrom : 1;
   int64_t per_bg = per_rec;
   pl->pscan_sel_h.clear();
-  for (int g = 0; g < nbg; ++g) {
-    const int c = bg_chrom < 0 ? g : bg_chrom;
-    const int64_t cb = d->chrom_off[(size_t)c], ce = d->chrom_off[(size_t)c + 1];
-    for (int64_t s = cb; s < ce; s += PROJ_CHUNK)
-      pl->pscan_sel_h.push_back(ProjSel{0xffffffffu, (uint32_t)g, (uint32_t)s, (uint32_t)std::min<int64_t>(s + PROJ_CHUNK, ce)});
-    per_bg = std::max<int64_t>(per_bg, ce - cb);
-  }
-  const int e = fixed_point(per_rec), e_bg = fixed_point(per_bg);
+  for (int g = 0; g < nbg; ++g)
+    per_bg = std::max<int64_t>(per_bg, push_chrom(pl->pscan_sel_h, d, bg_chrom < 0 ? g : bg_chrom, (uint32_t)g));
+  const int e = proj_fixed_point((unsigned __int128)per_rec), e_bg = proj_fixed_point((unsigned __int128)per_bg);
   if (e < 8 || e_bg < 8)
     return set_err(ctx, SFS2D_E_CAP, "project_scan: up to " + std::to_string(e < 8 ? per_rec : per_bg) +
                                          " SNPs in one grid leave fewer than 8 fraction bits in 64-bit sums");
@@ -2832,79 +2825,37 @@ int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_c
   if (e_bg_out) *e_bg_out = e_bg;
   const size_t nsel = pl->pscan_sel_h.size();
   if (nsel > 0xffffffffull) return set_err(ctx, SFS2D_E_ARG, "project_scan: more than 2^32 - 1 background pieces");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = CTX_STREAM(ctx);
-  if (!ctx->d_lf) {
-    int rc = dalloc(ctx, &ctx->d_lf, (size_t)PROJ_LF);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy(ctx->d_lf, proj_lf_table(), sizeof(double) * PROJ_LF, hipMemcpyHostToDevice));
-  }
+  if ((rc = proj_tables(ctx))) return rc;
   const size_t bgw = (size_t)nbg * (size_t)roww, lpn = (size_t)nbg * (size_t)lpw;
-  if (nsel > pl->pscan_sel_cap || bgw > pl->pscan_bg_cap || lpn > pl->pscan_lp_cap) {
-    HIPCHK(ctx, hipStreamSynchronize(st));   // an earlier call may still read what is replaced
-    auto grow = [&](auto** p, size_t* cap, size_t want) {
-      if (want <= *cap) return 0;
-      hipFree(*p);
-      *p = nullptr;
-      *cap = 0;
-      const int rc = dalloc(ctx, p, want);
-      if (rc) (void)hipGetLastError();
-      else *cap = want;
-      return rc;
-    };
-    int rc = grow(&pl->d_pscan_sel, &pl->pscan_sel_cap, nsel);
-    if (!rc) rc = grow(&pl->d_pscan_bg, &pl->pscan_bg_cap, bgw);
-    if (!rc) rc = grow(&pl->d_pscan_lp, &pl->pscan_lp_cap, lpn);
-    if (rc) return rc;
-  }
-  if (!out_dev && !pl->d_pscan && pl->nrec) {
-    int rc = dalloc(ctx, &pl->d_pscan, (size_t)pl->nrec);
-    if (rc) return rc;
-  }
-  if (lds + 4096 > 64 * 1024) {   // above the default limit the family opts in; per device the limit only grows
-    static std::mutex mu;
-    static std::map<int, size_t> granted;
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& have = granted[ctx->device];
-    if (lds > have) {
-      if (set_max_lds<ProjScan>(lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return set_err(ctx, SFS2D_E_CAP, "project_scan: the device refuses " + std::to_string(lds) +
-                                             " bytes of dynamic LDS for k_proj_scan");
-      }
-      have = lds;
-    }
-  }
-  int rc = 0;
+  bool synced = false;
+  sfs2d_projstat* out = nullptr;
+  if ((rc = reserve(ctx, st, pl->pscan_sel, nsel, &synced)) || (rc = reserve(ctx, st, pl->pscan_bg, bgw, &synced)) ||
+      (rc = reserve(ctx, st, pl->pscan_lp, lpn, &synced)) ||
+      (rc = call_out(ctx, st, pl->pscan_out, out_dev, (size_t)pl->nrec, &synced, &out)))
+    return rc;
+  // above the default limit the family opts in
+  if (lds + 4096 > 64 * 1024 && !grant_lds<ProjScan>(ctx, lds))
+    return set_err(ctx, SFS2D_E_CAP, "project_scan: the device refuses " + std::to_string(lds) +
+                                         " bytes of dynamic LDS for k_proj_scan");
   const ProjScan::Fn ks = variant(ctx, ProjScan{pl->cnt}, "k_proj_scan", &rc);
   if (!ks) return rc;
-  sfs2d_projstat* out = out_dev ? out_dev : pl->d_pscan;
-  pl->pscan_last = out;
-  pl->pscan_nrec = pl->nrec;
+  pl->pscan_out.last = out;
+  pl->pscan_out.n = pl->nrec;
   if (pl->nrec == 0) return 0;
-  const sfs2d_window* recs = pl->last_out ? pl->last_out : pl->d_out;
   // the background chromosomes' rows by k_proj_win (chromosome entries, as sfs2d_plan_project launches them) ...
-  HIPCHK(ctx, hipMemsetAsync(pl->d_pscan_bg, 0, sizeof(unsigned long long) * bgw, st));
+  HIPCHK(ctx, hipMemsetAsync(pl->pscan_bg.p, 0, sizeof(unsigned long long) * bgw, st));
   if (nsel) {
-    HIPCHK(ctx, hipMemcpyAsync(pl->d_pscan_sel, pl->pscan_sel_h.data(), sizeof(ProjSel) * nsel, hipMemcpyHostToDevice, st));
-    const size_t wlds = sizeof(unsigned long long) * (size_t)roww;
-    const bool ldsh = proj_win_ldsh(ctx, wlds);
-    const ProjWin::Fn kw = variant(ctx, ProjWin{pl->cnt, ldsh}, "k_proj_win", &rc);
-    if (!kw) return rc;
-    const int per_cu = ldsh ? (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (wlds + 4096))) : 8;
-    const dim3 g((unsigned)std::min<int64_t>((int64_t)nsel, (int64_t)per_cu * ctx->ncu));
-    hipLaunchKernelGGL(kw, g, dim3(PROJ_BLOCK), ldsh ? wlds : 0, st, pl->K, d->counts, scan_src(pl), recs, pl->d_pscan_sel,
-                       ctx->d_lf, pl->d_pscan_bg, (uint32_t)nsel, (uint32_t)pl->nrec, (uint32_t)nbg, (uint32_t)d->n,
-                       (uint32_t)m1, (uint32_t)m2, std::ldexp(1.0, e_bg), 1ull << (62 - e_bg));
-    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(pl->pscan_sel.p, pl->pscan_sel_h.data(), sizeof(ProjSel) * nsel, hipMemcpyHostToDevice, st));
+    if ((rc = launch_proj_win(pl, recs, pl->pscan_sel.p, nsel, pl->pscan_bg.p, (uint32_t)nbg, m1, m2, e_bg))) return rc;
   }
   // ... their ln tables, and every record against its chromosome's
-  hipLaunchKernelGGL(k_proj_lp, dim3((unsigned)nbg), dim3(PROJ_BLOCK), 0, st, pl->d_pscan_bg, pl->d_pscan_lp, (uint32_t)m1,
+  hipLaunchKernelGGL(k_proj_lp, dim3((unsigned)nbg), dim3(PROJ_BLOCK), 0, st, pl->pscan_bg.p, pl->pscan_lp.p, (uint32_t)m1,
                      (uint32_t)m2, pl->K.fold);
   HIPCHK(ctx, hipGetLastError());
   const int per_cu = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds + 4096)));
   const dim3 g((unsigned)std::min<int64_t>(pl->nrec, (int64_t)per_cu * ctx->ncu));
-  hipLaunchKernelGGL(ks, g, dim3(PROJ_BLOCK), lds, st, pl->K, d->counts, scan_src(pl), recs, ctx->d_lf, pl->d_pscan_lp, out,
+  hipLaunchKernelGGL(ks, g, dim3(PROJ_BLOCK), lds, st, pl->K, d->counts, scan_src(pl), recs, ctx->d_lf, pl->pscan_lp.p, out,
                      (uint32_t)pl->nrec, (uint32_t)nbg, (uint32_t)d->n, (uint32_t)m1, (uint32_t)m2, bg_chrom < 0 ? 0 : 1,
                      std::ldexp(1.0, e), std::ldexp(1.0, -e), (uint32_t)e);
   HIPCHK(ctx, hipGetLastError());
@@ -2913,16 +2864,7 @@ int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_c
 
 int sfs2d_plan_project_scan_read(sfs2d_plan* pl, sfs2d_projstat* out_host, int64_t cap, int64_t* nrec_out) {
   if (!pl || !nrec_out) return SFS2D_E_ARG;
-  sfs2d_ctx* ctx = pl->ctx;
-  if (pl->pscan_nrec < 0) return set_err(ctx, SFS2D_E_ARG, "sfs2d_plan_project_scan_read before sfs2d_plan_project_scan");
-  *nrec_out = pl->pscan_nrec;
-  if (cap < pl->pscan_nrec) return set_err(ctx, SFS2D_E_CAP, "output capacity too small");
-  if (pl->pscan_nrec && !out_host) return SFS2D_E_ARG;
-  if (pl->pscan_nrec)
-    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->pscan_last, sizeof(sfs2d_projstat) * (size_t)pl->pscan_nrec,
-                               hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
-  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
-  return 0;
+  return read_last(pl, pl->pscan_out, out_host, cap, nrec_out, "sfs2d_plan_project_scan");
 }
 
 int sfs2d_plan_time(sfs2d_plan* pl, int iters, double* ms_run, double* ms_k1, double* ms_k2, double* ms_k3) {
@@ -3143,7 +3085,7 @@ static int bg_hist_impl(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_para
     if (e == hipSuccess) e = hipMemsetAsync(pl.d_repl, 0, sizeof(uint32_t) * REPL * K.nh, CTX_STREAM(ctx));
     if (e == hipSuccess) e = hipMemsetAsync(pl.d_err, 0, 4, CTX_STREAM(ctx));
     if (e == hipSuccess) e = hipMemsetAsync(pl.d_bcount, 0, 4, CTX_STREAM(ctx));
-    if (e == hipSuccess && pl.lds_hist && pl.bg_lds > 64 * 1024) set_max_lds<Prep>(pl.bg_lds);
+    if (e == hipSuccess && pl.lds_hist && pl.bg_lds > 64 * 1024) grant_lds<Prep>(ctx, pl.bg_lds);
     if (e == hipSuccess) rc = launch_prep(&pl, false);
     // (rc: a selection outside the table launched nothing; reported below, after the buffers are freed)
     if (!rc && e == hipSuccess && d_row) {

@@ -43,7 +43,8 @@ __device__ __forceinline__ void div_windows(const KParams& P, const uint32_t* __
                                             uint32_t nrec, uint32_t nsnp, uint32_t wave_id, uint32_t nwaves) {
   const int lane = threadIdx.x & (WAVE - 1);
   for (uint32_t s = wave_id; s < nrec; s += nwaves) {
-    const uint32_t rf = recs[s].flags & (SFS2D_W_EMPTY | SFS2D_W_EXTRA);
+    const RecRange rr = rec_range<false>(recs, s, nsnp);
+    const uint32_t rf = rr.flags, b = rr.b, e = rr.e;
     sfs2d_diversity o;
     memset(&o, 0, sizeof(o));
     o.flags = rf;
@@ -51,7 +52,6 @@ __device__ __forceinline__ void div_windows(const KParams& P, const uint32_t* __
       if (lane == 0) out[s] = o;
       continue;
     }
-    const uint32_t e = min(recs[s].end, nsnp), b = min(recs[s].begin, e);   // (never past the data set)
     double pi1 = 0.0, pi2 = 0.0, dxy = 0.0, th1 = 0.0, th2 = 0.0;
     unsigned long long af1 = 0, af2 = 0;
     uint32_t s1 = 0, s2 = 0, f1 = 0, f2 = 0;

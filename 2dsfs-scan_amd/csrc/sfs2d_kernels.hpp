@@ -478,6 +478,26 @@ __device__ __forceinline__ uint32_t cls_word(const KParams& P, uint32_t c) {
   return (k2 == nb2m1 ? B_LAST : k2) | (f1 << 16) | (f2 << 23) | B_VAR;
 }
 
+// Record s of a run as the post-scan kernels take it: its flags masked to EMPTY | EXTRA (non-zero: no window of
+// its own; b = e = 0 then, its range is not read) and its SNP range [b, e) -- e = min(end, nsnp), never past the data set,
+// and b = min(begin, e).  UNIFORM: the record is the workgroup's (scalar values by readfirstlane, uniform
+// branches on them); otherwise per lane.
+struct RecRange {
+  uint32_t flags, b, e;
+};
+template <bool UNIFORM>
+__device__ __forceinline__ RecRange rec_range(const sfs2d_window* __restrict__ recs, uint32_t s, uint32_t nsnp) {
+  auto rd = [](uint32_t v) { return UNIFORM ? __builtin_amdgcn_readfirstlane(v) : v; };
+  RecRange r;
+  r.b = r.e = 0u;
+  r.flags = rd(recs[s].flags) & (SFS2D_W_EMPTY | SFS2D_W_EXTRA);
+  if (!r.flags) {   // (the range is read only for a record that has one)
+    r.e = min(rd(recs[s].end), nsnp);
+    r.b = min(rd(recs[s].begin), r.e);
+  }
+  return r;
+}
+
 // cls_word's fields without the packing, for the scan kernels' SNP rows: the inner 2D key k2 (0: in no
 // inner bin; the excluded last bin and clamped out-of-grid keys included) and both folded inner 1D
 // bins, the latter in packed u16 arithmetic (v_perm, v_pk_sub / v_pk_min, a saturating v_pk_sub for the

@@ -81,10 +81,9 @@ __global__ __launch_bounds__(PROJ_BLOCK) void k_proj_lp(const unsigned long long
   if (tid <= m2) o[ngrid + m1 + 1u + tid] = in2 ? log((double)f2[tid]) - lnC : 0.0;
 }
 
-// Workgroup b takes the records [b nrec / G, (b + 1) nrec / G).  Per record: the SNP range streamed as k_proj_win
-// streams an entry (all 256 lanes over rows of 256 SNPs, PROJ_ROWS rows' loads in flight, every lane loads; a lane
-// owns its SNP and walks the support rectangle; the loop is k_proj_win's, kept apart so that kernel's code does not
-// change), the terms added with non-returning LDS atomics into the u64 grid at the FOLDED index; then, in place:
+// Workgroup b takes the records [b nrec / G, (b + 1) nrec / G).  Per record: the SNP range (rec_range) projected by
+// proj_walk, as k_proj_win projects an entry, the terms added with non-returning LDS atomics into the u64 grid at
+// the FOLDED index; then, in place:
 //   pass 1   the inner sum N (u64, exact) and every bin into the two folded marginals (integer LDS atomics)
 //   pass 2   per lane over its bins in index order x_k ((ln x_k - ln N) - lp_k) for x_k > 0, the word zeroed in the
 //            same pass (the next record of the workgroup starts from an empty grid); the 1D terms from the marginal
@@ -118,7 +117,8 @@ __global__ __launch_bounds__(PROJ_BLOCK) void k_proj_scan(KParams P, const uint3
   const bool in1 = tid >= 1u && 2u * tid < m1, in2 = tid >= 1u && 2u * tid < m2;
   for (uint32_t s = lo; s < hi; ++s) {
     // (the record is the workgroup's: scalar values, uniform branches around the barriers)
-    const uint32_t rflags = __builtin_amdgcn_readfirstlane(recs[s].flags) & (SFS2D_W_EMPTY | SFS2D_W_EXTRA);
+    const RecRange rr = rec_range<true>(recs, s, nsnp);
+    const uint32_t rflags = rr.flags, b = rr.b, e = rr.e;
     if (rflags) {   // no window of its own: the flags alone
       if (tid == 0) {
         sfs2d_projstat z = {};
@@ -127,49 +127,17 @@ __global__ __launch_bounds__(PROJ_BLOCK) void k_proj_scan(KParams P, const uint3
       }
       continue;
     }
-    const uint32_t e = min(__builtin_amdgcn_readfirstlane(recs[s].end), nsnp);   // (never past the data set)
-    const uint32_t b = min(__builtin_amdgcn_readfirstlane(recs[s].begin), e);
     const uint32_t c = bg_one ? 0u : __builtin_amdgcn_readfirstlane(recs[s].chrom);
-    for (uint32_t r0 = b; r0 < e; r0 += PROJ_ROWS * PROJ_BLOCK) {
-      uint32_t cw[PROJ_ROWS], w[PROJ_ROWS];
-#pragma unroll
-      for (int j = 0; j < PROJ_ROWS; ++j) {
-        const uint32_t k = r0 + PROJ_BLOCK * j + tid, kc = min(k, e - 1u);
-        const uint32_t cv = counts[kc];
-        cw[j] = k < e ? cv : 0u;   // (counts 0: an SNP in no spectrum)
-        if (!CNT) {
-          const uint32_t wv = bins[kc];
-          w[j] = k < e ? wv : 0u;   // (a bins word with no bin)
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < PROJ_ROWS; ++j) {
-        const uint32_t wj = CNT ? cls_word(P, cw[j]) : w[j];
-        const bool member = (bin_k2(wj) != 0u) | ((wj & B_LAST) != 0u);
-        const uint32_t cj = cw[j];
-        const uint32_t r1 = cj & 0xffu, a1 = (cj >> 8) & 0xffu, r2 = (cj >> 16) & 0xffu, a2 = cj >> 24;
-        const uint32_t n1c = r1 + a1, n2c = r2 + a2;   // u8 counts: n <= 510 < PROJ_LF
-        const bool used = member & (n1c >= m1) & (n2c >= m2);
-        const uint32_t nu = (uint32_t)__popcll(__ballot(used)), nd = (uint32_t)__popcll(__ballot(member & !used));
-        if ((tid & (WAVE - 1)) == 0) {
+    proj_walk<CNT>(
+        P, counts, bins, lf, b, e, m1, m2, scale,
+        [&](uint32_t nu, uint32_t nd) {
           if (nu) atomicAdd(H + ngrid, (unsigned long long)nu);
           if (nd) atomicAdd(H + ngrid + 1u, (unsigned long long)nd);
-        }
-        if (used) {
-          const uint32_t l1 = m1 > r1 ? m1 - r1 : 0u, h1 = min(m1, a1);
-          const uint32_t l2 = m2 > r2 ? m2 - r2 : 0u, h2 = min(m2, a2);
-          const double c1 = proj_lnc(lf, n1c, a1, m1), c2 = proj_lnc(lf, n2c, a2, m2);
-          for (uint32_t j1 = l1; j1 <= h1; ++j1) {
-            const double v1 = proj_w(lf, c1, n1c, a1, m1, j1) * scale;
-            for (uint32_t j2 = l2; j2 <= h2; ++j2) {
-              const unsigned long long t = (unsigned long long)__double2ll_rn(v1 * proj_w(lf, c2, n2c, a2, m2, j2));
-              const uint32_t k = j1 * w2 + j2;   // (j1 <= m1, j2 <= m2: inside the grid, and so is its mirror)
-              if (t) atomicAdd(H + ((fold && 2u * (j1 + j2) > m12) ? ngrid - 1u - k : k), t);
-            }
-          }
-        }
-      }
-    }
+        },
+        [&](uint32_t j1, uint32_t j2, unsigned long long t) {
+          const uint32_t k = j1 * w2 + j2;   // (j1 <= m1, j2 <= m2: inside the grid, and so is its mirror)
+          atomicAdd(H + ((fold && 2u * (j1 + j2) > m12) ? ngrid - 1u - k : k), t);
+        });
     __syncthreads();   // (every wavefront's adds are in)
     // pass 1
     unsigned long long part = 0ull;

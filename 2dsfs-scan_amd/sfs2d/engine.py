@@ -365,6 +365,21 @@ class Plan:
                                                               C.byref(n)))
         return out
 
+    def _selection(self, name, rec, grp, ngroups):
+        """``rec`` / ``grp`` / ``ngroups`` of ``spectra`` and ``project`` as the library takes them: the two arrays
+        (kept alive by the caller), their pointers, nsel and ngroups."""
+        r = None if rec is None else np.ascontiguousarray(np.asarray(rec, np.int64).reshape(-1))
+        g = None if grp is None else np.ascontiguousarray(np.asarray(grp, np.int32).reshape(-1))
+        if r is not None and g is not None and len(r) != len(g):
+            raise ValueError(f"{name}: rec and grp differ in length")
+        nsel = len(r) if r is not None else (len(g) if g is not None else self.nrec)
+        if ngroups is None:
+            ngroups = max(1, self.nrec if g is None else (int(g.max()) + 1 if len(g) else 1))
+        # (an empty array still passes a non-null pointer: a NULL means "every record" / "group i = record i")
+        rp = None if r is None else C.c_void_p(r.ctypes.data)
+        gp = None if g is None else C.c_void_p(g.ctypes.data)
+        return r, g, rp, gp, nsel, int(ngroups)
+
     def spectra(self, rec=None, grp=None, ngroups: Optional[int] = None,
                 out_dev_ptr: Optional[int] = None) -> Optional[np.ndarray]:
         """The spectra themselves of chosen records of this plan's last run, summed into groups
@@ -375,17 +390,7 @@ class Plan:
         its largest entry + 1.  A record listed twice is counted twice; on overlapping windows a group is the sum
         over its windows, not the spectrum of their union.  Any plan that has run, attached plans included.  With
         ``out_dev_ptr`` (a device buffer of ngroups rows) nothing is copied to the host and None is returned."""
-        r = None if rec is None else np.ascontiguousarray(np.asarray(rec, np.int64).reshape(-1))
-        g = None if grp is None else np.ascontiguousarray(np.asarray(grp, np.int32).reshape(-1))
-        if r is not None and g is not None and len(r) != len(g):
-            raise ValueError("spectra: rec and grp differ in length")
-        nsel = len(r) if r is not None else (len(g) if g is not None else self.nrec)
-        if ngroups is None:
-            ngroups = max(1, self.nrec if g is None else (int(g.max()) + 1 if len(g) else 1))
-        ngroups = int(ngroups)
-        # (an empty array still passes a non-null pointer: a NULL means "every record" / "group i = record i")
-        rp = None if r is None else C.c_void_p(r.ctypes.data)
-        gp = None if g is None else C.c_void_p(g.ctypes.data)
+        r, g, rp, gp, nsel, ngroups = self._selection("spectra", rec, grp, ngroups)
         self.eng.check(self.eng.lib.sfs2d_plan_spectra(self.h, rp, gp, nsel, ngroups,
                                                        C.c_void_p(out_dev_ptr) if out_dev_ptr else None))
         if out_dev_ptr:
@@ -407,16 +412,7 @@ class Plan:
         call chose; two calls give equal arrays.  With ``out_dev_ptr`` (a device buffer of ngroups rows of
         ``L.proj_row_words(m1, m2)`` int64) nothing is copied to the host and None is returned."""
         m1, m2 = int(m1), int(m2)
-        r = None if rec is None else np.ascontiguousarray(np.asarray(rec, np.int64).reshape(-1))
-        g = None if grp is None else np.ascontiguousarray(np.asarray(grp, np.int32).reshape(-1))
-        if r is not None and g is not None and len(r) != len(g):
-            raise ValueError("project: rec and grp differ in length")
-        nsel = len(r) if r is not None else (len(g) if g is not None else self.nrec)
-        if ngroups is None:
-            ngroups = max(1, self.nrec if g is None else (int(g.max()) + 1 if len(g) else 1))
-        ngroups = int(ngroups)
-        rp = None if r is None else C.c_void_p(r.ctypes.data)
-        gp = None if g is None else C.c_void_p(g.ctypes.data)
+        r, g, rp, gp, nsel, ngroups = self._selection("project", rec, grp, ngroups)
         e = C.c_int32()
         self.eng.check(self.eng.lib.sfs2d_plan_project(self.h, m1, m2, rp, gp, nsel, ngroups,
                                                        C.c_void_p(out_dev_ptr) if out_dev_ptr else None, C.byref(e)))
