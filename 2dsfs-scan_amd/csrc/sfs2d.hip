@@ -18,6 +18,9 @@
 // spectrum projected down to a common sample size, as int64 fixed-point rows; it writes its own output alone.
 // sfs2d_plan_project_scan enqueues k_proj_win over the background chromosomes, k_proj_lp and k_proj_scan
 // (sfs2d_projscan.hpp): T2D / T1D of every record at a common sample size, the window grids in LDS alone.
+// sfs2d_plan_project_null builds, once per run and projection, the pools of used SNPs sorted by (chromosome, called
+// counts) and their stratum table (k_pnull_keys, a stable radix sort, k_pnull_heads), then enqueues k_proj_null
+// (sfs2d_projnull.hpp): replicates of chosen records whose SNPs are redrawn among SNPs of equal called counts.
 // All device state a run touches (slot table, background replicas and counters, LDS) is left
 // zeroed by the run itself, so plans replay without memsets.
 #include <hip/hip_runtime.h>
@@ -43,6 +46,10 @@
 #include "sfs2d_spec.hpp"
 #include "sfs2d_proj.hpp"
 #include "sfs2d_projscan.hpp"
+#include "sfs2d_projnull.hpp"
+
+// the pool build's stable sort (set-up of sfs2d_plan_project_null, not a hot path)
+#include <rocprim/device/device_radix_sort.hpp>
 
 using namespace sfs2dk;
 
@@ -289,6 +296,22 @@ struct sfs2d_plan {
   DevBuf<unsigned long long> pscan_bg;   // their rows
   DevBuf<double> pscan_lp;               // and ln tables
   CallOut<sfs2d_projstat> pscan_out;     // records
+  // sfs2d_plan_project_null: the pools and the backgrounds' ln tables of (pnull_done, pnull_m1, pnull_m2) -- built
+  // by the first call after a run or with another projection, kept for the calls that follow --, the last call's
+  // selection, records and thin-slot counts
+  uint64_t pnull_done = 0;               // the executed run the pool was built from (0: none)
+  int32_t pnull_m1 = 0, pnull_m2 = 0;
+  PnullDims pnull_dims{0, 0};
+  DevBuf<uint32_t> pnull_pool;           // pool_idx: the SNPs sorted by stratum cell, stable (unused SNPs last)
+  DevBuf<uint2> pnull_tab;               // (start, size) per cell
+  std::vector<ProjSel> pnull_bgsel_h;    // the background chromosomes' selection,
+  DevBuf<ProjSel> pnull_bgsel;
+  DevBuf<unsigned long long> pnull_bg;   // their rows
+  DevBuf<double> pnull_lp;               // and ln tables
+  std::vector<uint32_t> pnull_sel_h;     // the entries' record indices
+  DevBuf<uint32_t> pnull_sel;
+  CallOut<sfs2d_projstat> pnull_out;     // records, entries x replicates
+  CallOut<uint32_t> pnull_thin;          // thin slots per entry
   int64_t maxsnp = 0;                    // plan_create's bound on the SNPs of one record (Fst's e, P16)
   // runs enqueued for EXECUTION, apart from `runs` (the parity of the buffers the next enqueued run takes): a run
   // enqueued into a graph capture counts when the graph is launched (sfs2d_graph_launch), not at the capture.  The
@@ -345,6 +368,8 @@ void plan_free(sfs2d_plan* p) {
   hipFree(p->spec_sel.p); hipFree(p->spec_out.own.p);
   hipFree(p->proj_sel.p); hipFree(p->proj_out.own.p);
   hipFree(p->pscan_sel.p); hipFree(p->pscan_bg.p); hipFree(p->pscan_lp.p); hipFree(p->pscan_out.own.p);
+  hipFree(p->pnull_pool.p); hipFree(p->pnull_tab.p); hipFree(p->pnull_bgsel.p); hipFree(p->pnull_bg.p); hipFree(p->pnull_lp.p);
+  hipFree(p->pnull_sel.p); hipFree(p->pnull_out.own.p); hipFree(p->pnull_thin.own.p);
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->tev) if (e) hipEventDestroy(e);
 }
@@ -466,6 +491,16 @@ struct ProjScan {   // k_proj_scan<CNT>
   static constexpr ProjScan at(int i) { return {bool(i & 1)}; }
   constexpr bool legal() const { return true; }
   template <int I> static constexpr Fn kernel() { constexpr ProjScan s = at(I); return k_proj_scan<s.cnt>; }
+};
+
+struct ProjNull {   // k_proj_null<CNT>
+  bool cnt;
+  using Fn = decltype(&k_proj_null<true>);
+  static constexpr int N = 2;
+  constexpr int index() const { return cnt; }
+  static constexpr ProjNull at(int i) { return {bool(i & 1)}; }
+  constexpr bool legal() const { return true; }
+  template <int I> static constexpr Fn kernel() { constexpr ProjNull s = at(I); return k_proj_null<s.cnt>; }
 };
 
 // entry I of family S's table: its kernel, instantiated only where the selection is legal
@@ -2784,6 +2819,31 @@ int sfs2d_plan_project_read(sfs2d_plan* pl, double* out_host, int64_t* used, int
 
 // ------------------------------------------------------------------------------------------ projected scan
 
+namespace {
+
+// The fixed points of a projected scan of this plan, shared by sfs2d_plan_project_scan and sfs2d_plan_project_null so
+// that observed and null values carry the same rounding -- windows: one record per grid; backgrounds: one chromosome
+// entry per row (section 18's rule for such a call) -- and the background chromosomes' selection (bg_chrom < 0:
+// every chromosome, group = chromosome; else that one, group 0).  SFS2D_E_CAP below 8 fraction bits.
+int pscan_fixed_points(sfs2d_plan* pl, const char* name, int32_t bg_chrom, std::vector<ProjSel>& sel, int* e_out,
+                       int* e_bg_out) {
+  const sfs2d_data* d = pl->data;
+  const int64_t per_rec = std::max<int64_t>(1, pl->maxsnp);
+  const int nbg = bg_chrom < 0 ? d->nchrom : 1;
+  int64_t per_bg = per_rec;
+  sel.clear();
+  for (int g = 0; g < nbg; ++g) per_bg = std::max<int64_t>(per_bg, push_chrom(sel, d, bg_chrom < 0 ? g : bg_chrom, (uint32_t)g));
+  const int e = proj_fixed_point((unsigned __int128)per_rec), e_bg = proj_fixed_point((unsigned __int128)per_bg);
+  if (e < 8 || e_bg < 8)
+    return set_err(pl->ctx, SFS2D_E_CAP, std::string(name) + ": up to " + std::to_string(e < 8 ? per_rec : per_bg) +
+                                             " SNPs in one grid leave fewer than 8 fraction bits in 64-bit sums");
+  *e_out = e;
+  *e_bg_out = e_bg;
+  return 0;
+}
+
+}  // namespace
+
 int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_chrom, sfs2d_projstat* out_dev,
                             int32_t* e_out, int32_t* e_bg_out) {
   if (!pl) return SFS2D_E_ARG;
@@ -2810,17 +2870,9 @@ int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_c
     return set_err(ctx, SFS2D_E_CAP, "project_scan: the (" + std::to_string(m1 + 1) + " x " + std::to_string(m2 + 1) +
                                          ") window grid takes " + std::to_string(lds + 4096) +
                                          " bytes of LDS, more than the 163840 of a compute unit");
-  // windows: one record per grid; backgrounds: one chromosome entry per row (section 18's rule for such a call)
-  const int64_t per_rec = std::max<int64_t>(1, pl->maxsnp);
   const int nbg = bg_chrom < 0 ? d->nchrom : 1;
-  int64_t per_bg = per_rec;
-  pl->pscan_sel_h.clear();
-  for (int g = 0; g < nbg; ++g)
-    per_bg = std::max<int64_t>(per_bg, push_chrom(pl->pscan_sel_h, d, bg_chrom < 0 ? g : bg_chrom, (uint32_t)g));
-  const int e = proj_fixed_point((unsigned __int128)per_rec), e_bg = proj_fixed_point((unsigned __int128)per_bg);
-  if (e < 8 || e_bg < 8)
-    return set_err(ctx, SFS2D_E_CAP, "project_scan: up to " + std::to_string(e < 8 ? per_rec : per_bg) +
-                                         " SNPs in one grid leave fewer than 8 fraction bits in 64-bit sums");
+  int e = 0, e_bg = 0;
+  if ((rc = pscan_fixed_points(pl, "project_scan", bg_chrom, pl->pscan_sel_h, &e, &e_bg))) return rc;
   if (e_out) *e_out = e;
   if (e_bg_out) *e_bg_out = e_bg;
   const size_t nsel = pl->pscan_sel_h.size();
@@ -2865,6 +2917,183 @@ int sfs2d_plan_project_scan(sfs2d_plan* pl, int32_t m1, int32_t m2, int32_t bg_c
 int sfs2d_plan_project_scan_read(sfs2d_plan* pl, sfs2d_projstat* out_host, int64_t cap, int64_t* nrec_out) {
   if (!pl || !nrec_out) return SFS2D_E_ARG;
   return read_last(pl, pl->pscan_out, out_host, cap, nrec_out, "sfs2d_plan_project_scan");
+}
+
+// ------------------------------------------------------------------------------------------ projected null
+
+namespace {
+
+// The pools of (the plan's last executed run, m1, m2): pool_idx -- every SNP index sorted by its stratum cell
+// (chromosome, n1c - m1, n2c - m2), stable, so ascending within a stratum, the SNPs in no pool last -- and the dense
+// table of (start, size) per cell; beside them the background chromosomes' rows and ln tables at e_bg.  Built by the
+// first call after a run or with another projection and kept on the plan.  Set-up, not the hot path: the sort is
+// rocprim's stable radix sort over the cell index's bits; its key and value arrays are freed when it is done.
+int pnull_pools(sfs2d_plan* pl, const sfs2d_window* recs, int32_t m1, int32_t m2, int e_bg, bool* synced) {
+  sfs2d_ctx* ctx = pl->ctx;
+  const sfs2d_data* d = pl->data;
+  if (pl->pnull_done == pl->done && pl->pnull_m1 == m1 && pl->pnull_m2 == m2) return 0;
+  pl->pnull_done = 0;
+  hipStream_t st = CTX_STREAM(ctx);
+  const uint32_t n = (uint32_t)d->n, nchrom = (uint32_t)d->nchrom;
+  // u8 counts: a called count is at most 510, whatever the data set reports (wrapped device data: nothing)
+  const uint32_t mx1 = std::max<uint32_t>((uint32_t)m1, std::min<uint32_t>(510u, d->max_nc1));
+  const uint32_t mx2 = std::max<uint32_t>((uint32_t)m2, std::min<uint32_t>(510u, d->max_nc2));
+  const PnullDims D{mx1 - (uint32_t)m1 + 1u, mx2 - (uint32_t)m2 + 1u};
+  const unsigned long long ncell = (unsigned long long)nchrom * D.d1 * D.d2;
+  if (ncell >= 0xffffffffull)
+    return set_err(ctx, SFS2D_E_CAP, "project_null: " + std::to_string(nchrom) + " chromosomes x " + std::to_string(D.d1) +
+                                         " x " + std::to_string(D.d2) + " called-count pairs do not fit a 32-bit stratum index");
+  int rc = 0;
+  const int64_t ngrid = (int64_t)(m1 + 1) * (m2 + 1), roww = ngrid + 2, lpw = ngrid + (m1 + 1) + (m2 + 1);
+  const size_t nsel = pl->pnull_bgsel_h.size(), bgw = (size_t)nchrom * (size_t)roww, lpn = (size_t)nchrom * (size_t)lpw;
+  if ((rc = reserve(ctx, st, pl->pnull_pool, (size_t)n, synced)) || (rc = reserve(ctx, st, pl->pnull_tab, (size_t)ncell, synced)) ||
+      (rc = reserve(ctx, st, pl->pnull_bgsel, nsel, synced)) || (rc = reserve(ctx, st, pl->pnull_bg, bgw, synced)) ||
+      (rc = reserve(ctx, st, pl->pnull_lp, lpn, synced)))
+    return rc;
+  // the backgrounds, as sfs2d_plan_project_scan builds them
+  HIPCHK(ctx, hipMemsetAsync(pl->pnull_bg.p, 0, sizeof(unsigned long long) * bgw, st));
+  if (nsel) {
+    HIPCHK(ctx, hipMemcpyAsync(pl->pnull_bgsel.p, pl->pnull_bgsel_h.data(), sizeof(ProjSel) * nsel, hipMemcpyHostToDevice, st));
+    if ((rc = launch_proj_win(pl, recs, pl->pnull_bgsel.p, nsel, pl->pnull_bg.p, nchrom, m1, m2, e_bg))) return rc;
+  }
+  hipLaunchKernelGGL(k_proj_lp, dim3(nchrom), dim3(PROJ_BLOCK), 0, st, pl->pnull_bg.p, pl->pnull_lp.p, (uint32_t)m1,
+                     (uint32_t)m2, pl->K.fold);
+  HIPCHK(ctx, hipGetLastError());
+  // the pools
+  uint32_t *key_in = nullptr, *key_out = nullptr, *val_in = nullptr;
+  void* tmp = nullptr;
+  auto done = [&](int code) {
+    hipFree(key_in); hipFree(key_out); hipFree(val_in); hipFree(tmp);   // (hipFree waits for the device)
+    return code;
+  };
+  if ((rc = dalloc(ctx, &key_in, (size_t)n)) || (rc = dalloc(ctx, &key_out, (size_t)n)) || (rc = dalloc(ctx, &val_in, (size_t)n)))
+    return done(rc);
+  const dim3 gk((n + 255u) / 256u);
+  if (pl->cnt)
+    hipLaunchKernelGGL(k_pnull_keys<true>, gk, dim3(256), 0, st, pl->K, d->counts, scan_src(pl), d->d_chrom_off, nchrom, n,
+                       (uint32_t)m1, (uint32_t)m2, D, (uint32_t)ncell, key_in, val_in);
+  else
+    hipLaunchKernelGGL(k_pnull_keys<false>, gk, dim3(256), 0, st, pl->K, d->counts, scan_src(pl), d->d_chrom_off, nchrom, n,
+                       (uint32_t)m1, (uint32_t)m2, D, (uint32_t)ncell, key_in, val_in);
+  if (hipGetLastError() != hipSuccess) return done(set_err(ctx, SFS2D_E_HIP, "project_null: k_pnull_keys launch"));
+  size_t tmp_bytes = 0;
+  // (the key of a SNP in no pool is ncell and sorts last: the bits of ncell are all the sort reads)
+  unsigned bits = 1;
+  while (bits < 32 && (ncell >> bits) != 0) ++bits;
+  if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, key_in, key_out, val_in, pl->pnull_pool.p, (size_t)n, 0u, bits, st) != hipSuccess)
+    return done(set_err(ctx, SFS2D_E_HIP, "project_null: radix sort (size query)"));
+  if (hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 1)) != hipSuccess) {
+    (void)hipGetLastError();
+    return done(set_err(ctx, SFS2D_E_NOMEM, "project_null: radix sort workspace"));
+  }
+  if (rocprim::radix_sort_pairs(tmp, tmp_bytes, key_in, key_out, val_in, pl->pnull_pool.p, (size_t)n, 0u, bits, st) != hipSuccess)
+    return done(set_err(ctx, SFS2D_E_HIP, "project_null: radix sort"));
+  if (hipMemsetAsync(pl->pnull_tab.p, 0, sizeof(uint2) * (size_t)std::max<unsigned long long>(1, ncell), st) != hipSuccess)
+    return done(set_err(ctx, SFS2D_E_HIP, "project_null: stratum table memset"));
+  for (int phase = 0; phase < 2; ++phase)
+    hipLaunchKernelGGL(k_pnull_heads, gk, dim3(256), 0, st, key_out, n, (uint32_t)ncell, pl->pnull_tab.p, phase);
+  if (hipGetLastError() != hipSuccess) return done(set_err(ctx, SFS2D_E_HIP, "project_null: k_pnull_heads launch"));
+  if (hipStreamSynchronize(st) != hipSuccess) return done(set_err(ctx, SFS2D_E_HIP, "project_null: pool build"));
+  done(0);
+  pl->pnull_done = pl->done;
+  pl->pnull_m1 = m1;
+  pl->pnull_m2 = m2;
+  pl->pnull_dims = D;
+  return 0;
+}
+
+}  // namespace
+
+int sfs2d_plan_project_null(sfs2d_plan* pl, int32_t m1, int32_t m2, const sfs2d_null_params* np, const int64_t* rec,
+                            int64_t nsel, sfs2d_projstat* out_dev, uint32_t* thin_dev, int32_t* e_out, int32_t* e_bg_out) {
+  if (!pl) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  const sfs2d_data* d = pl->data;
+  if (!np) return set_err(ctx, SFS2D_E_ARG, "project_null: null argument");
+  const sfs2d_window* recs = nullptr;
+  int rc = post_ready(pl, "project_null", &recs);
+  if (rc) return rc;
+  if (pl->prm.bg_mode == SFS2D_BG_SUPPLIED)
+    return set_err(ctx, SFS2D_E_ARG, "project_null: a plan with a supplied background has no projected background "
+                                     "(only per-chromosome plans)");
+  if (m1 < 2 || m1 > pl->K.n1 || m2 < 2 || m2 > pl->K.n2)
+    return set_err(ctx, SFS2D_E_ARG, "project_null: (m1, m2) = (" + std::to_string(m1) + ", " + std::to_string(m2) +
+                                         ") outside [2, " + std::to_string(pl->K.n1) + "] x [2, " + std::to_string(pl->K.n2) + "]");
+  if (np->replicates < 1) return set_err(ctx, SFS2D_E_ARG, "project_null: replicates must be >= 1");
+  if (pl->nrec > 0xffffffffll) return set_err(ctx, SFS2D_E_ARG, "project_null: more than 2^32 - 1 records");
+  if (nsel < 0) return set_err(ctx, SFS2D_E_ARG, "project_null: nsel must be >= 0");
+  if (!rec && nsel != pl->nrec)
+    return set_err(ctx, SFS2D_E_ARG, "project_null: rec == NULL selects every record in order: nsel must be the plan's record count");
+  pl->pnull_sel_h.resize(rec ? (size_t)nsel : 0);
+  for (int64_t i = 0; rec && i < nsel; ++i) {
+    if (rec[i] < 0 || rec[i] >= pl->nrec)
+      return set_err(ctx, SFS2D_E_ARG, "project_null: entry " + std::to_string(i) + ": record " + std::to_string(rec[i]) +
+                                           " outside [0, " + std::to_string(pl->nrec) + ")");
+    pl->pnull_sel_h[(size_t)i] = (uint32_t)rec[i];
+  }
+  const unsigned long long nout = (unsigned long long)nsel * np->replicates;
+  if (nout > (1ull << 26))
+    return set_err(ctx, SFS2D_E_CAP, "project_null: more than 2^26 records in one call (split the selection)");
+  const size_t lds = sizeof(unsigned long long) * pscan_lds_words((uint32_t)m1, (uint32_t)m2);
+  if (lds + 4096 > 160 * 1024)
+    return set_err(ctx, SFS2D_E_CAP, "project_null: the (" + std::to_string(m1 + 1) + " x " + std::to_string(m2 + 1) +
+                                         ") window grid takes " + std::to_string(lds + 4096) +
+                                         " bytes of LDS, more than the 163840 of a compute unit");
+  int e = 0, e_bg = 0;
+  if ((rc = pscan_fixed_points(pl, "project_null", -1, pl->pnull_bgsel_h, &e, &e_bg))) return rc;
+  if (e_out) *e_out = e;
+  if (e_bg_out) *e_bg_out = e_bg;
+  hipStream_t st = CTX_STREAM(ctx);
+  if ((rc = proj_tables(ctx))) return rc;
+  bool synced = false;
+  sfs2d_projstat* out = nullptr;
+  uint32_t* thin = nullptr;
+  if ((rc = reserve(ctx, st, pl->pnull_sel, pl->pnull_sel_h.size(), &synced)) ||
+      (rc = call_out(ctx, st, pl->pnull_out, out_dev, (size_t)nout, &synced, &out)) ||
+      (rc = call_out(ctx, st, pl->pnull_thin, thin_dev, (size_t)nsel, &synced, &thin)))
+    return rc;
+  if (lds + 4096 > 64 * 1024 && !grant_lds<ProjNull>(ctx, lds))
+    return set_err(ctx, SFS2D_E_CAP, "project_null: the device refuses " + std::to_string(lds) +
+                                         " bytes of dynamic LDS for k_proj_null");
+  const ProjNull::Fn kn = variant(ctx, ProjNull{pl->cnt}, "k_proj_null", &rc);
+  if (!kn) return rc;
+  if (nout && (rc = pnull_pools(pl, recs, m1, m2, e_bg, &synced))) {
+    pl->pnull_out.last = nullptr; pl->pnull_out.n = -1;
+    pl->pnull_thin.last = nullptr; pl->pnull_thin.n = -1;
+    return rc;
+  }
+  pl->pnull_out.last = out;
+  pl->pnull_out.n = (int64_t)nout;
+  pl->pnull_thin.last = thin;
+  pl->pnull_thin.n = nsel;
+  if (nout == 0) return 0;
+  if (rec)
+    HIPCHK(ctx, hipMemcpyAsync(pl->pnull_sel.p, pl->pnull_sel_h.data(), sizeof(uint32_t) * (size_t)nsel, hipMemcpyHostToDevice, st));
+  const int per_cu = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds + 4096)));
+  const dim3 g((unsigned)std::min<unsigned long long>(nout, (unsigned long long)per_cu * ctx->ncu));
+  const uint2 key = make_uint2((uint32_t)np->seed, (uint32_t)(np->seed >> 32));
+  hipLaunchKernelGGL(kn, g, dim3(PROJ_BLOCK), lds, st, pl->K, d->counts, scan_src(pl), recs, rec ? pl->pnull_sel.p : nullptr,
+                     ctx->d_lf, pl->pnull_lp.p, pl->pnull_tab.p, pl->pnull_pool.p, out, thin, (uint32_t)nout, np->replicates, key,
+                     (uint32_t)d->nchrom, (uint32_t)d->n, (uint32_t)m1, (uint32_t)m2, pl->pnull_dims, std::ldexp(1.0, e),
+                     std::ldexp(1.0, -e), (uint32_t)e);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int sfs2d_plan_project_null_read(sfs2d_plan* pl, sfs2d_projstat* out_host, uint32_t* thin_host, int64_t cap, int64_t* nrec_out) {
+  if (!pl || !nrec_out) return SFS2D_E_ARG;
+  sfs2d_ctx* ctx = pl->ctx;
+  // (out_host NULL: the records are not wanted -- they may be in the caller's device buffer -- and cap is not read)
+  const int rc = read_ready(pl, pl->pnull_out, out_host ? cap : INT64_MAX, nrec_out, "sfs2d_plan_project_null");
+  if (rc) return rc;
+  if (pl->pnull_thin.n > 0 && thin_host)
+    HIPCHK(ctx, hipMemcpyAsync(thin_host, pl->pnull_thin.last, sizeof(uint32_t) * (size_t)pl->pnull_thin.n, hipMemcpyDeviceToHost,
+                               CTX_STREAM(ctx)));
+  if (pl->pnull_out.n > 0 && out_host)
+    HIPCHK(ctx, hipMemcpyAsync(out_host, pl->pnull_out.last, sizeof(sfs2d_projstat) * (size_t)pl->pnull_out.n,
+                               hipMemcpyDeviceToHost, CTX_STREAM(ctx)));
+  HIPCHK(ctx, hipStreamSynchronize(CTX_STREAM(ctx)));
+  return 0;
 }
 
 int sfs2d_plan_time(sfs2d_plan* pl, int iters, double* ms_run, double* ms_k1, double* ms_k2, double* ms_k3) {

@@ -62,7 +62,9 @@ EXPORTS = [
     "sfs2d_plan_spectra", "sfs2d_plan_spectra_read",
     "sfs2d_plan_project", "sfs2d_plan_project_read", "sfs2d_project_weights",
     "sfs2d_plan_project_scan", "sfs2d_plan_project_scan_read",
+    "sfs2d_plan_project_null", "sfs2d_plan_project_null_read",
 ]
+PNULL_THIN = 8    # SFS2D_PNULL_THIN: a stratum with fewer SNPs makes a slot "thin" (sfs2d_plan_project_null)
 ABI_VERSION = 2   # SFS2D_ABI_VERSION of include/sfs2d.h
 
 
@@ -199,6 +201,8 @@ def lib():
     L.sfs2d_project_weights.argtypes = [i32, i32, i32, vp]
     L.sfs2d_plan_project_scan.argtypes = [vp, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
     L.sfs2d_plan_project_scan_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.sfs2d_plan_project_null.argtypes = [vp, i32, i32, C.POINTER(NullParams), vp, i64, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.sfs2d_plan_project_null_read.argtypes = [vp, vp, vp, i64, C.POINTER(i64)]
     L.sfs2d_data_synth_sims.argtypes = [vp, C.POINTER(SynthParams), vp, vp, i32, vp, i32, C.POINTER(vp)]
     L.sfs2d_data_read.argtypes = [vp, vp, vp, i64]
     L.sfs2d_ctx_use_own_stream.argtypes = [vp]

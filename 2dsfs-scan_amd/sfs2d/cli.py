@@ -61,6 +61,12 @@ low bins that missing calls give a window.  One more file per ``--window`` / ``-
 regions), ``snp_count, n_used, n_dropped, T2D_proj, T1D_pop1_proj, T1D_pop2_proj, new_term_pop1_proj,
 new_term_pop2_proj, T2D_diff_proj``; each prints the share of its SNPs that the projection dropped.  Every other
 file is what it is without the flag.
+
+``--project-null R`` (with ``--project-scan``; ``--null-seed`` is shared) appends to every such file the p-values of
+the projected statistics from a null that keeps each window's called counts (projected_scan(replicates=R); DESIGN.md
+section 20): ``p_T2D_proj, p_T1D_pop1_proj, p_T1D_pop2_proj, p_new_term_pop1_proj, p_new_term_pop2_proj,
+p_T2D_diff_proj`` and ``n_thin``, the window's used SNPs whose stratum of equal called counts holds fewer than 8
+SNPs; each file prints the share of used slots that are thin.  Without the flag every file is what it was.
 """
 from __future__ import annotations
 
@@ -175,14 +181,19 @@ def parse_project(text, n1p: int, n2p: int, flag: str = "--project"):
     return m1, m2
 
 
-def write_projscan_csv(path, rows, chr_ids, regions=None):
+def write_projscan_csv(path, rows, chr_ids, regions=None, null=False):
     """``<stem>_projscan<M1>x<M2>.csv``: the rows of projected_scan (sfs2d.spectra.PROJSCAN_COLUMNS) behind the
     window's chromosome, start and end, with a leading ``name`` column for ``regions`` (one row per region in the
-    caller's order).  A None is an empty field."""
+    caller's order).  ``null``: the rows carry projected_scan(replicates=...)'s p-values and n_thin, appended as
+    seven more columns.  A None is an empty field."""
     from .spectra import PROJSCAN_COLUMNS
     head = ["chromosome", "window_start", "window_end"]
+    cols = list(PROJSCAN_COLUMNS)
+    if null:   # (--project-null: the seven columns of sfs2d.projnull behind the others)
+        from .projnull import PROJNULL_COLUMNS
+        cols += PROJNULL_COLUMNS
     with open(path, "w", newline="") as fh:
-        w = csv.DictWriter(fh, fieldnames=(["name"] if regions is not None else []) + head + PROJSCAN_COLUMNS)
+        w = csv.DictWriter(fh, fieldnames=(["name"] if regions is not None else []) + head + cols)
         w.writeheader()
         if regions is not None:
             for key, s in zip(regions.keys(), regions.slot.tolist()):
@@ -258,6 +269,9 @@ def main(argv=None):
     ap.add_argument("--project-scan", default=None, metavar="M1,M2",
                     help="T2D / T1D of every window at the common sample size M1 / M2 (projected spectra against the "
                          "projected chromosome) -> one <stem>_projscan<M1>x<M2>.csv per window output")
+    ap.add_argument("--project-null", type=int, default=None, metavar="R",
+                    help="with --project-scan: append p-values from R replicates per window whose SNPs are redrawn "
+                         "among SNPs of equal called counts (seven columns; --null-seed is the draws' seed)")
     ap.add_argument("--out-prefix", default="stats")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="VCF parser threads (0 = all)")
@@ -291,6 +305,12 @@ def main(argv=None):
             pscan = parse_project(a.project_scan, a.pop1_size, a.pop2_size, "--project-scan")
         except ValueError as e:
             ap.error(str(e))
+    if a.project_null is not None:
+        if pscan is None:
+            ap.error("--project-null needs --project-scan")
+        if a.project_null < 1:
+            ap.error("--project-null must be >= 1")
+    pnkw = dict(replicates=a.project_null, seed=a.null_seed) if a.project_null is not None else {}
     null = a.null_replicates is not None
     block = None
     if a.null_block is not None:
@@ -341,12 +361,17 @@ def main(argv=None):
         # (the new flag alone: a scan of its own per file, nothing of the calls above changes)
         if pscan is None:
             return
-        rows = obj.projected_scan(packed, pscan, **geometry)
+        rows = obj.projected_scan(packed, pscan, **geometry, **pnkw)
         path = "{}_projscan{}x{}.csv".format(stem, *pscan)
-        write_projscan_csv(path, rows, chr_ids, geometry.get("regions"))
+        write_projscan_csv(path, rows, chr_ids, geometry.get("regions"), **(dict(null=True) if pnkw else {}))
         outs.append(path)
         used, dropped = (sum(r[k] for r in rows.values()) for k in ("n_used", "n_dropped"))
         print(f"projected_scan {pscan}: {len(rows)} windows, {_dropped_share(used, dropped)} -> {path}", file=sys.stderr)
+        if pnkw:
+            thin = sum(r["n_thin"] for r in rows.values())
+            share = f"{100.0 * thin / used:.2f} %" if used else "no used SNPs"
+            print(f"project_null R = {a.project_null}: {thin} of {used} used slots are thin ({share}: strata of fewer "
+                  f"than 8 SNPs)", file=sys.stderr)
 
     def regions_out(res):
         if rg is None:

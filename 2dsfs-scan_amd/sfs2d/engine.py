@@ -449,6 +449,55 @@ class Plan:
                                                                  C.byref(n)))
         return out
 
+    def project_null(self, m1: int, m2: int, replicates: int, seed: int = 0, rec=None,
+                     out_dev_ptr: Optional[int] = None):
+        """The null of the projected scan (sfs2d_plan_project_null): ``replicates`` replicates
+        of every record of this plan's last run (``rec`` None) or of the records ``rec``, in which every used SNP is
+        replaced by one drawn among the used SNPs of its chromosome with the same called counts (n1c, n2c), evaluated
+        as ``project_scan`` evaluates a window.  Returns ``(PROJSTAT_DTYPE[len(rec) * replicates], uint32[len(rec)])``:
+        record t * replicates + r is replicate r of entry t, and per entry the number of used slots whose stratum
+        holds fewer than ``L.PNULL_THIN`` SNPs.  ``self.project_null_e`` / ``self.project_null_e_bg`` are the fixed
+        points (``project_scan``'s for this plan and projection).  The entries are split over calls of at most 2**22
+        records; a draw is a function of (seed, record, replicate, slot) and the data, so neither the split nor the
+        order of ``rec`` changes an entry's records.  With ``out_dev_ptr`` (a device buffer of len(rec) * replicates
+        records) the records stay on the device and only the thin-slot counts are returned."""
+        from .null import MAX_CALL_RECORDS
+        R = int(replicates)
+        if R < 0 or R > 0xFFFFFFFF:
+            raise ValueError("replicates out of range")
+        r = None if rec is None else np.ascontiguousarray(np.asarray(rec, np.int64).reshape(-1))
+        nent = self.nrec if r is None else len(r)
+        npar = L.NullParams(seed=int(seed) & 0xFFFFFFFFFFFFFFFF, replicates=R)
+        per = max(1, MAX_CALL_RECORDS // max(1, R))   # entries per call
+        e, eb = C.c_int32(), C.c_int32()
+        parts, thin = [], np.zeros(nent, np.uint32)
+        isz = L.PROJSTAT_DTYPE.itemsize
+        for a in range(0, max(1, nent), per):
+            b = min(nent, a + per)
+            if r is None and a == 0 and b == nent:
+                part, pp = None, None   # (every record in order)
+            else:
+                part = np.ascontiguousarray(r[a:b]) if r is not None else np.arange(a, b, dtype=np.int64)
+                pp = C.c_void_p(part.ctypes.data)   # (an empty array still passes a non-null pointer)
+            out = C.c_void_p(out_dev_ptr + a * R * isz) if out_dev_ptr else None
+            self.eng.check(self.eng.lib.sfs2d_plan_project_null(self.h, int(m1), int(m2), C.byref(npar), pp, b - a, out,
+                                                                None, C.byref(e), C.byref(eb)))
+            n = C.c_int64()
+            th = np.zeros(b - a, np.uint32)
+            if out_dev_ptr:   # (the thin-slot counts alone; the records stay where they are)
+                self.eng.check(self.eng.lib.sfs2d_plan_project_null_read(self.h, None, L.ptr(th) if len(th) else None, 0,
+                                                                         C.byref(n)))
+            else:
+                got = np.zeros((b - a) * R, dtype=L.PROJSTAT_DTYPE)
+                self.eng.check(self.eng.lib.sfs2d_plan_project_null_read(self.h, L.ptr(got) if len(got) else None,
+                                                                         L.ptr(th) if len(th) else None, len(got), C.byref(n)))
+                parts.append(got)
+            thin[a:b] = th
+        self.project_null_e, self.project_null_e_bg = e.value, eb.value
+        if out_dev_ptr:
+            return None, thin
+        return (np.concatenate(parts) if parts else np.zeros(0, L.PROJSTAT_DTYPE)), thin
+
     def bg_buffer(self):
         p = C.c_void_p()
         nb = C.c_int64()

@@ -982,7 +982,7 @@ class LikelihoodInference_jointSFS:
 
     # ------------------------------------------------------------------ projected scan (extension)
     def projected_scan(self, data_dict, project, window_size=None, snp_window_size=None, step_size=None, regions=None,
-                       background_chromosome=None):
+                       background_chromosome=None, replicates=None, seed=0):
         """T2D and T1D of every window at a common sample size: the scan's statistics from spectra projected down
         hypergeometrically to ``project`` = (m1, m2) haploid samples, each window against its chromosome projected
         the same way (``background_chromosome``: that chromosome for every window, as scan_chooseChr).  The scans
@@ -996,7 +996,24 @@ class LikelihoodInference_jointSFS:
         (sfs2d.spectra.project_scan_rows): None for an empty foreground or background, +inf where the window
         touches a bin its background lacks.  The statistic is the closed form 2 sum x_k (ln(x_k / N) - ln(b_k /
         B)) over the inner bins; the reference's exact 0.0 for proportional spectra is not reproduced.  The
-        reference has no projection."""
+        reference has no projection.
+        ``replicates`` = R: every row gains p_T2D_proj, p_T1D_pop1_proj, p_T1D_pop2_proj, p_new_term_pop1_proj,
+        p_new_term_pop2_proj, p_T2D_diff_proj and n_thin (sfs2d.projnull): the projected T
+        still grows as a window's called counts approach the projection, so each window is judged against R
+        replicates of itself in which every used SNP is redrawn among the used SNPs of its chromosome with the
+        same called counts (k_proj_null, on the GPU; ``seed`` the draws'); p = (1 + exceedances) / (R + 1), None
+        where the statistic is None; n_thin counts the window's used SNPs whose stratum holds fewer than 8 SNPs
+        (redrawn from almost nothing).  Not with ``background_chromosome`` (a foreign pool can have empty strata)
+        nor distributed: NotImplementedError."""
+        if replicates is not None:
+            if background_chromosome is not None:
+                raise NotImplementedError("projected_scan: replicates with background_chromosome (the null draws from "
+                                          "each window's own chromosome; a foreign pool can have empty strata)")
+            if getattr(self, "distributed", False):
+                raise NotImplementedError("projected_scan: replicates on a distributed object")
+            if isinstance(replicates, bool) or int(replicates) != replicates or int(replicates) < 1:
+                raise ValueError(f"projected_scan: replicates must be an integer >= 1, got {replicates!r}")
+            replicates = int(replicates)
         self._no_distributed_spectra("projected_scan")
         project = self._check_project(project)
         p = self._pack(data_dict)
@@ -1017,14 +1034,26 @@ class LikelihoodInference_jointSFS:
                 pl.check()
                 recs = pl.read()
                 stats = pl.project_scan(*project, bg_chrom)
+                if replicates is not None:
+                    null, thin = pl.project_null(*project, replicates, seed)
             finally:
                 pl.close()
         finally:
             dev.close()
         if rg is not None:   # (one row per region, in the caller's order)
             order = rg.slot.tolist()
-            return SP.project_scan_rows(recs[order], stats[order], list(rg.keys()))
-        return SP.project_scan_rows(recs, stats, post.record_labels(recs, p, kind, w, step))
+            rows, labels = SP.project_scan_rows(recs[order], stats[order], list(rg.keys())), list(rg.keys())
+        else:
+            order = None
+            labels = post.record_labels(recs, p, kind, w, step)
+            rows = SP.project_scan_rows(recs, stats, labels)
+        if replicates is not None:
+            from sfs2d import projnull as PN
+            pv = PN.project_pvalues(stats, null, replicates)
+            if order is not None:
+                pv, thin = {k: v[order] for k, v in pv.items()}, thin[order]
+            PN.add_pvalue_columns(rows, labels, pv, thin)
+        return rows
 
     # ------------------------------------------------------------------ SFS primitives
     def calculate_2d_sfs(self, data_dict):

@@ -42,7 +42,8 @@ extern "C" {
  * an argument); sfs2d_plan_diversity / _diversity_read and sfs2d_diversity added (additive);
  * sfs2d_plan_create_regions / sfs2d_plan_attach_regions added (additive: the intervals are arguments);
  * sfs2d_plan_spectra / _spectra_read added (additive); sfs2d_plan_project / _project_read and
- * sfs2d_project_weights added (additive); sfs2d_plan_project_scan / _project_scan_read added (additive) */
+ * sfs2d_project_weights added (additive); sfs2d_plan_project_scan / _project_scan_read added (additive);
+ * sfs2d_plan_project_null / _project_null_read added (additive) */
 #define SFS2D_ABI_VERSION 2
 
 /* status codes */
@@ -508,6 +509,50 @@ int sfs2d_plan_project_scan(sfs2d_plan* plan, int32_t m1, int32_t m2, int32_t bg
 /* copy the last sfs2d_plan_project_scan call's records to host (synchronises); SFS2D_E_CAP: cap below the record
  * count (*nrec_out holds it); SFS2D_E_ARG: no such call since the plan was created */
 int sfs2d_plan_project_scan_read(sfs2d_plan* plan, sfs2d_projstat* out_host, int64_t cap, int64_t* nrec_out);
+/* The null of the projected scan: replicates of chosen records of the plan's last run in which
+ * every used SNP is replaced by one drawn among the used SNPs of its chromosome with the SAME called counts.  The
+ * projected T still grows as a window's called counts approach (m1, m2) -- a SNP called in exactly m alleles adds an
+ * indicator to the grid, one called in n > m a spread-out hypergeometric row -- so a null that keeps each window's
+ * called counts is the one that can judge it; under missingness independent of frequency it is exact conditional on
+ * the window's coverage.  (m1, m2), the last run, membership, "used" (member & n1c >= m1 & n2c >= m2), the weights,
+ * the per-term rounding at 2^-e, the joint fold, the three statistics and their NaN / +inf rules are
+ * sfs2d_plan_project_scan's.
+ *   pool, stratum  the pool of chromosome c is its used SNPs; the stratum of a used SNP is the set of the pool's SNPs
+ *                  with the same (n1c, n2c) (called alleles per population), in ascending SNP index; a SNP is in its
+ *                  own stratum, so none is empty
+ *   entry          a record index s = rec[t] of the last run (rec == NULL: every record, nsel = the record count);
+ *                  each entry gets np->replicates = R replicates; output record t R + r is replicate r of entry t.  An
+ *                  EMPTY / EXTRA source record gives R records with its flags and zeros
+ *   slot i of replicate r  SNP k = begin + i of the record's clamped range.  A SNP that is not used draws nothing.  A
+ *                  used SNP with stratum (start, size) in its chromosome's pool draws
+ *                    c = philox4x32(counter (i >> 1, r, s, chrom + 1), key (seed & 0xffffffff, seed >> 32));
+ *                    x64 = c.x | c.y << 32 for even i, c.z | c.w << 32 for odd i;
+ *                    SNP pool_idx[start + mulhi64(x64, size)]
+ *                  -- integers only, a function of (seed, s, r, i) and the data, whatever the launch geometry and
+ *                  however a selection is split over calls
+ *   record         what sfs2d_plan_project_scan would write for a window made of the drawn SNPs, against the record's
+ *                  chromosome; *e_out / *e_bg_out are exactly those sfs2d_plan_project_scan reports for this plan and
+ *                  (m1, m2); n_used / n_dropped are the window's
+ *   thin           one uint32 per entry: the used slots whose stratum holds fewer than SFS2D_PNULL_THIN SNPs (such a
+ *                  slot is redrawn from almost nothing, which narrows the null; reported, not acted on)
+ * The pools (the SNPs sorted stably by chromosome and called counts, and a dense table of (start, size) per chromosome
+ * and called-count pair) are built by the first call after a run or with another (m1, m2) and kept on the plan.
+ * out_dev: nsel R records on the device; thin_dev: nsel uint32 (NULL = plan-owned, read with
+ * sfs2d_plan_project_null_read).  Enqueued on the ctx stream; attached, sliding, regions, SNP-count and filtered plans
+ * and wrapped device data as sfs2d_plan_project_scan.  Writes out_dev, thin_dev and its own buffers alone.
+ * SFS2D_E_ARG, the reason in sfs2d_last_error: a plan that has not run, m_k < 2 or m_k > 2 pop_size_k, a plan with a
+ * supplied background, replicates < 1, a record index outside the plan's records; SFS2D_E_CAP: more than 2^26 records
+ * in one call, a grid that does not fit the LDS of a compute unit, fewer than 8 fraction bits; SFS2D_E_NOMEM.
+ * A background chromosome for every record (a foreign pool can have empty strata), supplied backgrounds, block
+ * bootstraps (strata break adjacency) and size classes (every window has its own null) are not offered. */
+#define SFS2D_PNULL_THIN 8
+int sfs2d_plan_project_null(sfs2d_plan* plan, int32_t m1, int32_t m2, const sfs2d_null_params* np, const int64_t* rec,
+                            int64_t nsel, sfs2d_projstat* out_dev, uint32_t* thin_dev, int32_t* e_out, int32_t* e_bg_out);
+/* copy the last sfs2d_plan_project_null call's records (out_host NULL: not wanted, cap is not read) and thin-slot
+ * counts (thin_host NULL: not wanted) to host (synchronises); cap counts records; SFS2D_E_CAP: cap below the record count (*nrec_out holds it); SFS2D_E_ARG: no
+ * such call since the plan was created */
+int sfs2d_plan_project_null_read(sfs2d_plan* plan, sfs2d_projstat* out_host, uint32_t* thin_host, int64_t cap,
+                                 int64_t* nrec_out);
 /* launch geometry (threads per grid) of k_prep and of the scan kernel: matches the Grid_Size column
  * of rocprofv3 kernel traces, so profiles can be joined to a plan */
 int sfs2d_plan_grids(const sfs2d_plan* plan, int64_t* prep_threads, int64_t* scan_threads);
