@@ -271,6 +271,8 @@ struct sfs2d_plan {
   bool fst_mask = true;           // Fst in the scan: the data set has SNPs with < 2 called alleles (k_scan_w FST 3 / 5)
   bool gate = false;              // Fst in the scan, folded, called counts within (n1, n2): k_scan_w's GATE variants
   bool lean = false;              // gate, fixed-bp slot records, n1p, n2p <= 31: k_scan_w's LEAN variants (same results)
+  bool tri = false;               // lean, n1 = n2, the workgroup within SCAN_WT_LDS: k_scan_wt (same results)
+  int sb = 8, r1 = R1;            // k_scan_w(t): windows per batched finish, lane copies of the 1D window histograms
   int nfst = 0;                   // k_bg_slice's extra Fst workgroups
   // bootstrap null (sfs2d_plan_null_run): the last call's task table and records (a read before any call: 0 records)
   std::vector<NullTask> ntask_h;
@@ -415,6 +417,16 @@ struct ScanW {   // k_scan_w<P16, FUSED, FST, CNT, GATE, LEAN>
   // Fst in the scan is a counts plan's; GATE and LEAN (a gated variant) are built for it alone
   constexpr bool legal() const { return fst < 2 ? !gate && !lean : cnt && (gate || !lean); }
   template <int I> static constexpr Fn kernel() { constexpr ScanW s = at(I); return k_scan_w<s.p16, s.fused, s.fst, s.cnt, s.gate, s.lean>; }
+};
+
+struct ScanWT {   // k_scan_wt<P16, FUSED, FMASK, SBN, R1N>: the lean variants on a triangle-packed window histogram
+  bool p16, fused, fmask, sb32, r8;   // batches of 32 windows instead of 8; 8 lane copies of the 1D histograms instead of 4
+  using Fn = void (*)(SCAN_W_ARGS);
+  static constexpr int N = 32;
+  constexpr int index() const { return p16 | fused << 1 | fmask << 2 | sb32 << 3 | r8 << 4; }
+  static constexpr ScanWT at(int i) { return {bool(i & 1), bool(i & 2), bool(i & 4), bool(i & 8), bool(i & 16)}; }
+  constexpr bool legal() const { return true; }
+  template <int I> static constexpr Fn kernel() { constexpr ScanWT s = at(I); return k_scan_wt<s.p16, s.fused, s.fmask, s.sb32 ? 32 : 8, s.r8 ? 8 : R1>; }
 };
 
 struct ScanGW {   // k_scan_gw<P16, FST, CNT, TRI>
@@ -575,6 +587,8 @@ ScanW scan_w_sel(const sfs2d_plan* pl) {
   // window loop's tail specialised for fixed-bp slots and n1p, n2p <= 31)
   return {pl->p16, pl->fused, fst, pl->cnt, in_scan && (pl->gate || pl->lean), in_scan && pl->lean};
 }
+// (tri plans are lean ones: counts, Fst in the scan, gated)
+ScanWT scan_wt_sel(const sfs2d_plan* pl) { return {pl->p16, pl->fused, pl->fst_mask, pl->sb == 32, pl->r1 == 8}; }
 // (large grids: Fst from k_prep's sums, taken by the scan -- unless window kernels wrote it, fst_win)
 ScanGW scan_gw_sel(const sfs2d_plan* pl) { return {pl->p16, prep_sums_fst(pl), pl->cnt, pl->cnt && pl->K.ntri}; }
 ScanG scan_g_sel(const sfs2d_plan* pl) { return {pl->p16, prep_sums_fst(pl), pl->cnt}; }
@@ -594,6 +608,11 @@ ScanGW occ_standin(ScanGW s) { s.fst = s.cnt = true; return s; }
 constexpr ScanW SCAN_W_FIT = {true, true, 1, true, false, false};
 constexpr ScanW scan_w_fst_fit(bool p16) { return {p16, true, 2, true, false, false}; }
 constexpr Prep prep_lds_fit(bool fst) { return {true, true, true, true, false, fst, false}; }
+
+// k_scan_wt's workgroup, static and dynamic LDS together, at most: half a CU's 160 KB
+constexpr size_t SCAN_WT_LDS = 80 * 1024;
+// ... and the fewest windows per resident wavefront for which plan_create takes it
+constexpr double SCAN_WT_MIN_WPW = 8.0;
 
 // template arguments of the scan kernel being launched: {P16, FUSED, FST, CNT, GATE, TRI}, -1 where it has none
 void set_variant(sfs2d_plan* pl, int p16, int fused, int fst, int cnt, int gate, int tri) {
@@ -619,7 +638,8 @@ int launch_scan(sfs2d_plan* pl, sfs2d_window* out) {
                        pl->d_ctr, (int)(pl->runs & 1), pl->d_leafsum, pl->d_bg1d, 0, pl->d_gscr, pl->nscr);
   } else if (pl->G == WAVE) {
     const ScanW s = scan_w_sel(pl);
-    const ScanW::Fn k = variant(pl->ctx, s, "k_scan_w", &rc);
+    // (tri: the lean selection's k_scan_wt, reported as the lean variant it equals; sfs2d_plan_scan_packing tells)
+    const ScanW::Fn k = pl->tri ? variant(pl->ctx, scan_wt_sel(pl), "k_scan_wt", &rc) : variant(pl->ctx, s, "k_scan_w", &rc);
     if (!k) return rc;
     set_variant(pl, s.p16, s.fused, s.fst, s.cnt, s.gate, -1);   // (LEAN: a gated variant, gate = 1)
     hipExtLaunchKernelGGL(k, grid, dim3(SBLOCK), pl->scan_lds,
@@ -1202,6 +1222,9 @@ struct Knobs {
   const char* fused = std::getenv("SFS2D_FUSED");            // 0 / 1: small-grid tables sliced / fused
   const char* fst_scan = std::getenv("SFS2D_FST_SCAN");      // 0: Fst from k_prep's sums, not summed in the scan
   const char* lean = std::getenv("SFS2D_LEAN");              // 0: the gated variants where the lean ones apply
+  const char* tri = std::getenv("SFS2D_TRI");                // 0: the lean variants where the triangle-packed ones apply; 1: packed below SCAN_WT_MIN_WPW too
+  const char* sb = std::getenv("SFS2D_SB");                  // A/B: 8 / 32 windows per batched finish of a tri plan
+  const char* r1 = std::getenv("SFS2D_R1");                  // A/B: 4 / 8 lane copies of a tri plan's 1D window histograms
   const char* slots_once = std::getenv("SFS2D_SLOTS_ONCE");  // 0: index plans write their slot table every run
   const char* wgs = std::getenv("SFS2D_WGS");                // tuning: scan workgroups in all
   const char* gwwin = std::getenv("SFS2D_GWWIN");            // tuning: k_scan_gw windows per workgroup of a small chromosome
@@ -1539,6 +1562,37 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   // each: the LEAN variants (SFS2D_LEAN=0: the gated variants, for comparison -- the results are the same)
   pl->lean = pl->gate && bp && K.n1p <= 31 && K.n2p <= 31;
   if (env.lean) pl->lean = pl->lean && env.lean[0] != '0';
+  // lean plans with n1 = n2: the window histogram packed into its reachable bins (k_scan_wt), and the LDS that
+  // frees spent on batches of 32 windows and 8 lane copies of the 1D histograms -- while the workgroup, static LDS
+  // included, stays within SCAN_WT_LDS, so that two of them share a CU; otherwise the lean variant as it was.
+  // Only for plans with at least SCAN_WT_MIN_WPW windows per resident wavefront (wpw, above): with up to 8 a
+  // wavefront flushes as often in batches of 32 as in batches of 8, and the plan would pay the packed index's 16
+  // VALU per row-pair block for nothing (config 2, ~0.7 windows per wavefront: +2% per pass).
+  // SFS2D_TRI=0: the lean variant, for comparison (the results are the same); SFS2D_TRI=1: the packed variant
+  // whatever the windows per wavefront (the tests' small genomes), still within SCAN_WT_LDS
+  // (SFS2D_SB / SFS2D_R1: the arms with one ingredient less, for comparison; any other value is refused, for every
+  // plan, so that a mistyped comparison does not measure the default)
+  const std::string sbv = env.sb ? env.sb : "32", r1v = env.r1 ? env.r1 : "8";
+  if ((sbv != "8" && sbv != "32") || (r1v != "4" && r1v != "8")) {
+    delete pl;
+    return set_err(ctx, SFS2D_E_ARG, "SFS2D_SB must be 8 or 32 and SFS2D_R1 4 or 8 (the instantiations k_scan_wt has)");
+  }
+  const bool tri_gate = wpw >= SCAN_WT_MIN_WPW || (env.tri && env.tri[0] == '1');
+  if (pl->lean && K.n1 == K.n2 && !(env.tri && env.tri[0] == '0') && tri_gate) {
+    const int sb = sbv == "8" ? 8 : 32, r1 = r1v == "4" ? 4 : 8;
+    const int nh2 = (K.nb2 + K.n1) / 2 + 1;
+    const int h2w = pl->p16 ? (((nh2 + 1) / 2 + 3) & ~3) : ((nh2 + 3) & ~3);
+    const int per = (h2w + r1 * (K.n1p + 1) + r1 * (K.n2p + 1) + 3) & ~3;
+    const size_t hist_words = std::max<size_t>((size_t)(SBLOCK / WAVE) * per, (size_t)FUSED_VCNT + K.nt + 16);
+    const size_t lds = sizeof(double) * (size_t)(((K.nt + 1) & ~1) + LNT + LNF + 2 * (size_t)pl->K.rtn) + hist_words * 4;
+    const ScanWT fit = {pl->p16, true, true, sb == 32, r1 == 8};
+    if (lds + static_lds(fit, SCAN_WT_LDS) <= SCAN_WT_LDS) {
+      pl->tri = true;
+      pl->sb = sb;
+      pl->r1 = r1;
+      pl->scan_lds = lds;
+    }
+  }
   const PwTree pw = pw_plan(K.nb2 - 3);
   pl->fst_mask = data->low_nc;
   pl->fst_win = pl->sliced && bp && pl->fst && !pl->fst_scan;
@@ -1566,6 +1620,7 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   pl->nfst = pl->fst_win && !slide ? (int)std::min<int64_t>(1024, std::max<int64_t>(1, (pl->nslots + 7) / 8)) : 0;   // ~1 window per wave
   if (pl->scan_lds > 64 * 1024) {   // (k_scan_gw's: with its occupancy, above)
     grant_lds<ScanW>(ctx, pl->scan_lds);
+    grant_lds<ScanWT>(ctx, pl->scan_lds);
     grant_lds<ScanG>(ctx, pl->scan_lds);
   }
   if (pl->extra_lds > 64 * 1024) grant_lds<ScanExtra>(ctx, pl->extra_lds);
@@ -1578,7 +1633,8 @@ static int plan_create(sfs2d_ctx* ctx, const sfs2d_data* data, const sfs2d_param
   if (pl->G == WAVE || pl->gw) {
     // (the grid is one dispatch wave of resident workgroups: occupancy of the variant's stand-in, occ_standin)
     int occ = pl->gw ? occupancy(occ_standin(scan_gw_sel(pl)), WAVE, pl->scan_lds)
-                     : occupancy(occ_standin(scan_w_sel(pl)), SBLOCK, pl->scan_lds);
+                     : pl->tri ? occupancy(scan_wt_sel(pl), SBLOCK, pl->scan_lds)
+                               : occupancy(occ_standin(scan_w_sel(pl)), SBLOCK, pl->scan_lds);
     if (occ < 1) occ = 1;
     if (prm->scan_wgs_per_cu > 0 && (int)prm->scan_wgs_per_cu < occ) occ = (int)prm->scan_wgs_per_cu;
     int64_t cap = (int64_t)occ * ctx->ncu;
@@ -1889,6 +1945,15 @@ int sfs2d_plan_scan_variant(const sfs2d_plan* pl, int* p16, int* fused, int* fst
   int* const o[6] = {p16, fused, fst, cnt, gate, tri};
   for (int i = 0; i < 6; ++i)
     if (o[i]) *o[i] = pl->variant[i];
+  return 0;
+}
+
+int sfs2d_plan_scan_packing(const sfs2d_plan* pl, int* tri, int* sb, int* r1) {
+  if (!pl) return SFS2D_E_ARG;
+  const bool w = pl->G == WAVE && !pl->gw;
+  if (tri) *tri = w ? (pl->tri ? 1 : 0) : -1;
+  if (sb) *sb = w ? pl->sb : -1;
+  if (r1) *r1 = w ? pl->r1 : -1;
   return 0;
 }
 

@@ -33,6 +33,8 @@
 //   k_scan_w      the hot loop (small grids): one wavefront per window, 8 per workgroup sharing the
 //                 background's log-proportion table and the D / x ln x tables in LDS; bins streamed
 //                 with 16-B loads; one fp64 DPP reduction per spectrum; one 64-B record per window.
+//   k_scan_wt     k_scan_w's lean variants for n1 = n2 on a triangle-packed window histogram, with batches of 32
+//                 windows per finish and 8 lane copies of the 1D window histograms (same results).
 //   k_scan_gw     large grids: k_scan_w's loop in one-wavefront workgroups, tables read from L2.
 //   k_scan_g      grids too large for k_scan_gw: one workgroup per window (exact evaluation).
 //   k_scan_extra  combined_scan's final-window helper (quirk Q9).
@@ -85,7 +87,14 @@ constexpr int R1GW = SFS2D_GW_R1;
 // sum (and clear) the RR replicas of one 1D bin word group (RR consecutive words, 4 * RR-B aligned)
 template <int RR>
 __device__ __forceinline__ uint32_t take_replicas(uint32_t* p, uint32_t shift) {
-  if (RR == 4) {
+  if (RR == 8) {   // (two 16-B reads)
+    uint4* q = reinterpret_cast<uint4*>(p);
+    const uint4 v = q[0], u = q[1];
+    q[0] = make_uint4(0, 0, 0, 0);
+    q[1] = make_uint4(0, 0, 0, 0);
+    return (v.x >> shift) + (v.y >> shift) + (v.z >> shift) + (v.w >> shift) + (u.x >> shift) + (u.y >> shift) +
+           (u.z >> shift) + (u.w >> shift);
+  } else if (RR == 4) {
     uint4* q = reinterpret_cast<uint4*>(p);
     const uint4 v = *q;
     *q = make_uint4(0, 0, 0, 0);
@@ -1702,20 +1711,23 @@ struct TabFused {    // k_scan_w's own table: lp in LDS, counts summed from this
   }
 };
 
-template <int G, bool P16, int S1, bool CNT, class Tab>
+// TRI (k_scan_w's packed window histogram, see scan_w_small): H2 is indexed by the packed bin, the table by the key.
+template <int G, bool P16, int S1, bool CNT, bool TRI = false, class Tab>
 __device__ __forceinline__ WinOut eval_exact(const KParams& P, const uint32_t* __restrict__ bins, uint32_t b,
                                              uint32_t e, const Tab& T, const BgHead& hb,
                                              const double* __restrict__ lnx, uint32_t* H2, uint32_t* H1a,
                                              uint32_t* H1b, double* redd, unsigned long long* redu) {
+  static_assert(!TRI || G == WAVE, "the packed histogram is k_scan_w's");
   const int lane = threadIdx.x & (G - 1);
   const bool floatv = hb.flags & BGF_FLOATV;
+  [[maybe_unused]] const uint32_t triC = (uint32_t)(P.nb2 + P.n1);
   uint32_t c_var = 0, c2 = 0, c_last = 0, c1a = 0, c1b = 0;
   for (uint32_t i = b + lane; i < e; i += G) {
     const uint32_t w = snp_word<CNT>(P, bins, i);
     const uint32_t k2 = bin_k2(w), g1 = bin_g1(w), g2 = bin_g2(w);
     c_var += (w & B_VAR) ? 1u : 0u;
     c_last += (w & B_LAST) ? 1u : 0u;
-    if (k2) { ++c2; h2_add<P16>(H2, k2); }
+    if (k2) { ++c2; h2_add<P16>(H2, TRI ? min(k2, triC - k2) : k2); }
     if (g1) { ++c1a; atomicAdd(&H1a[g1 * S1], 1u); }
     if (g2) { ++c1b; atomicAdd(&H1b[g2 * S1], 1u); }
   }
@@ -1778,7 +1790,7 @@ __device__ __forceinline__ WinOut eval_exact(const KParams& P, const uint32_t* _
     const uint32_t w = snp_word<CNT>(P, bins, i);
     const uint32_t k2 = bin_k2(w), g1 = bin_g1(w), g2 = bin_g2(w);
     if (k2) {
-      const uint32_t x = h2_take<P16>(H2, k2);
+      const uint32_t x = h2_take<P16>(H2, TRI ? min(k2, triC - k2) : k2);
       if (x) {
         const PL t = T.at(k2);
         s2 += (double)x * (lnx_of(lnx, x) - t.lp);
@@ -2048,8 +2060,8 @@ __device__ __forceinline__ void fused_table(int nb2, int nh, int nt, int n1p, in
 }
 
 // K3 for small grids.  Workgroup LDS: [lp table of the chunk's background (nt doubles, rounded up
-// to even) | D | F | per wave: 2D bins (u16-packed when P16) | R1 x folded pop1 1D | R1 x pop2 1D |
-// 64 trash words].
+// to even) | D | F | per wave: 2D bins (u16-packed when P16) | R1N x folded pop1 1D | R1N x pop2 1D]
+// (R1N lane copies of each 1D bin: R1, or 8 in k_scan_wt; TRI: the 2D bins packed, see scan_w_small).
 // FUSED (per-chromosome backgrounds): the workgroup builds its chromosome's table in the prologue
 // from this run's k_prep replicas (the k_bg_slice computation, in the histogram area as scratch),
 // clears its share of the other parity's replicas for the next run, and the first workgroup of a
@@ -2637,7 +2649,14 @@ __device__ __forceinline__ void lds_copy_d(double* dst, const double* __restrict
 // and the last-bin rule are compile-time constants, so the general 1D end pass, the five wave_sum_all sums and
 // the nlast / nvar pass are not in the kernel; the ln-of-totals loads are issued as soon as their counts are
 // known; P16: the batch's counts are stored unclamped (a window holds < 65536 SNPs).  Same bits as GATE alone.
-template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false, bool LEAN = false>
+// TRI (LEAN plans with n1 = n2 = n; k_scan_wt): a gated key kk = x1 (n + 1) + x2 has x1 + x2 <= n, so the wave's 2D
+// window histogram holds only the (n / 2 + 1)(n + 1) reachable bins: with C = (n + 1)^2 + n the packed bin is
+// min(kk, C - kk), which folds row x1 > n / 2, reversed, into the free tail of row n + 1 - x1 (injective on
+// x1 + x2 <= n, fixes 0).  Only the histogram index is packed -- kw[], the clears, the over-LNT correction,
+// eval_exact's adds and takes -- and the lp table is not, so every output bit is the lean variant's.  The LDS this
+// frees goes to SBN, the windows per batched finish, and R1N, the lane copies of the 1D window histograms.
+template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false, bool LEAN = false, bool TRI = false, int SBN = 8,
+          int R1N = R1>
 // (wgi: the work item -- chunks[wgi] -- and nwg the items of the launch: k_scan_w's block index and grid)
 __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_t nwg, SCAN_W_ARGS) {
   constexpr bool FSTIN = FST >= 2;
@@ -2645,13 +2664,17 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
   static_assert(!FSTIN || CNT, "Fst in the scan reads the counts");
   static_assert(!GATE || CNT, "the gate is a property of the counts the scan classifies");
   static_assert(!LEAN || (GATE && FSTIN), "the lean window loop is built for the gated Fst-in-scan plans");
+  static_assert(LEAN || (!TRI && SBN == 8 && R1N == R1), "the packed histogram and what its room buys are the lean class's");
+  static_assert(SBN >= 8 && SBN <= WAVE && (SBN & (SBN - 1)) == 0, "a batch is a power of two of at most a wavefront's lanes");
+  static_assert(R1N == 1 || R1N == 2 || R1N == 4 || R1N == 8, "take_replicas' copies");
   if (LEAN) mode_bp = 1;   // (the lean class has fixed-bp slot records)
   constexpr int DT = LNT;   // D(r) entries in LDS
-  constexpr int R1U = R1;
+  constexpr int R1U = R1N;
   constexpr int NWV = SBLOCK / WAVE;
-  // windows per batch (see flush; LDS-limited: the 2 KB of the retired trash words; 16 with two 1D
-  // replicas instead of four measured 1-2 us faster than 8 with two: not worth the replicas)
-  constexpr int SB = 8;
+  // windows per batch (see flush), SBN: 8 in k_scan_w, whose LDS leaves no room for more (round 6: 16 with two 1D
+  // copies instead of four measured 1-2 us faster than 8 with two, not worth the copies); 32 in k_scan_wt's default,
+  // out of the LDS the packed histogram frees -- a quarter of the flushes and of the cold row fetches after them
+  constexpr int SB = SBN;
   __shared__ BgHead sh_hb;
   __shared__ double sh_bd[NWV][3][SB];      // batch: the three sums of window j
   __shared__ uint32_t sh_bu[NWV][5][SB];    // batch: slot, begin, n2 | n2_all, n1a | n1b, nsnp | nvar
@@ -2673,8 +2696,11 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
   // FSTIN: rtn (1/n, 1/(n(n-1))) pairs
   const int rtn = FSTIN ? P.rtn : 0;
   uint32_t* HB = reinterpret_cast<uint32_t*>(RT + rtn);
-  const int h2w = P16 ? ((P.nb2 + 1) / 2 + 3) & ~3 : (P.nb2 + 3) & ~3;
-  const int h1w = R1 * (P.n1p + 1), h1wb = R1 * (P.n2p + 1);
+  // TRI: C of the packed bin, and the (C + 1) / 2 bins it reaches (C is odd)
+  [[maybe_unused]] const uint32_t triC = TRI ? (uint32_t)(P.nb2 + P.n1) : 0u;
+  const int nh2 = TRI ? (P.nb2 + P.n1) / 2 + 1 : P.nb2;
+  const int h2w = P16 ? ((nh2 + 1) / 2 + 3) & ~3 : (nh2 + 3) & ~3;
+  const int h1w = R1U * (P.n1p + 1), h1wb = R1U * (P.n2p + 1);
   const int per = (h2w + h1w + h1wb + 3) & ~3;   // (16-B rows; no trash words: SNPs outside the 2D SFS skip the atomic)
   uint32_t* W = HB + wv * per;
   uint32_t* H1a = W + h2w;
@@ -2909,11 +2935,11 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       const uint32_t xe = xn != 0xffffu ? xb + xn : (mode_bp ? slots[xs].y : xb + P.ws);
       WinOut x;
       if (FUSED) {
-        x = eval_exact<WAVE, P16, R1, CNT>(P, bins, xb, xe,
+        x = eval_exact<WAVE, P16, R1U, CNT, TRI>(P, bins, xb, xe,
                                       TabFused{LPl, Rc, rs, P.nb2, P.n1, P.n2, P.n1p, P.h1a, P.h1b, P.t1a, P.t1b}, hb,
                                       lnx, W, H1a, H1b, nullptr, nullptr);
       } else {
-        x = eval_exact<WAVE, P16, R1, CNT>(P, bins, xb, xe, TabLocal{tab + (size_t)bg * P.nt, LPl}, hb, lnx, W, H1a, H1b,
+        x = eval_exact<WAVE, P16, R1U, CNT, TRI>(P, bins, xb, xe, TabLocal{tab + (size_t)bg * P.nt, LPl}, hb, lnx, W, H1a, H1b,
                                       nullptr, nullptr);
       }
       if (lane == 0) {
@@ -3007,7 +3033,7 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
     // prefetched registers (a row wholly past e is skipped; SNPs past e are w = 0, outside every
     // spectrum).  Per SNP: the 2D LDS atomic (u16 halves) returns the SNP's rank r in its bin and the
     // SNP adds D(r) - lp_k (telescoping: sum_k x_k ln x_k = sum_i D(r_i)); the folded 1D bins are
-    // counted in lane & 3 replicas, every SNP slot in one bin of each (the excluded bins 0 and n_p too:
+    // counted in R1N lane copies (lane & (R1N - 1)), every SNP slot in one bin of each (the excluded bins 0 and n_p too:
     // dropped at the window's end, which derives n1a / n1b from them).  An SNP outside the 2D spectrum
     // skips the 2D atomic and takes rank 0: D(0) = 0, LPl[0] = 0 (it used to add 0 to a lane-private
     // trash word: 2 KB of LDS per workgroup, now the batch's).  n2 is a wave-uniform ballot count.
@@ -3073,9 +3099,11 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
         else { k2 = bin_k2(w); gp = bin_g1(w) | (bin_g2(w) << 16); }
         in2[q] = k2 != 0u;   // (one compare: the ballot, the atomic's exec mask, the rank's select)
         n2 += __popcll(__ballot(in2[q]));
-        // low five bits: (k2 & 1) << 4, the u16 half's shift
-        const uint32_t x = (CNT ? k2 : w) << 4;
-        const uint32_t word = P16 ? (k2 >> 1) : k2;   // (k2 = 0: word 0, cleared after the window anyway)
+        // (TRI: the histogram's bin is the packed one; the rank's table entry below stays the key's)
+        const uint32_t kh = TRI ? min(k2, triC - k2) : k2;
+        // low five bits: (kh & 1) << 4, the u16 half's shift
+        const uint32_t x = (CNT ? kh : w) << 4;
+        const uint32_t word = P16 ? (kh >> 1) : kh;   // (k2 = 0: word 0, cleared after the window anyway)
         // (v_lshlrev_b32 / v_bfe_u32 read the shift's low five bits: no mask; C's << would need one)
         uint32_t one2 = 1u;
         if (P16) asm("v_lshlrev_b32 %0, %1, 1" : "=v"(one2) : "v"(x));
@@ -3095,7 +3123,7 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
         // words measured slower: profiles/r06p_scan_bin0_ballot_ab.txt)
         // (the bin's address base + bin * BS1 as one 16-bit multiply-add per population, the second on gp's
         // upper half: scaling the pair, masking and adding took four operations)
-        constexpr int BS1 = 4 * R1;   // LDS bytes per 1D bin (an inline constant)
+        constexpr int BS1 = 4 * R1U;   // LDS bytes per 1D bin (an inline constant)
         static_assert(BS1 <= 64, "the multiplier must be an inline constant");
         uint32_t u1, u2;
         asm("v_mad_u32_u16 %0, %1, %3, %2" : "=v"(u1) : "v"(gp), "v"(a1b), "n"(BS1));
@@ -3212,6 +3240,26 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
     if (clampd) {
       constexpr uint32_t L1 = LNT - 1;
       const double fl = (double)L1 * lnx[L1];   // F(LNT-1), as k_init_lnx's table entry
+      if (TRI) {
+        // the lean variant's walk over the unpacked words, each reachable bin read at its packed place: a lane's
+        // sum takes the same terms in the same order (unreachable bins hold 0 there; here they have no place)
+        static_assert(!TRI || CNT, "the packed histogram needs the counts' keys");
+        // (kb / (n + 1) as a multiplication: exact for kb < 4096 and n + 1 <= 63, the lean class's grids -- the
+        // quotient's error kb e / ((n + 1) 2^20), e <= n + 1, stays below 1 / 256 < 1 / (n + 1))
+        const uint32_t np1 = (uint32_t)P.n1 + 1u;
+        const uint32_t rcp = (1u << 20) / np1 + 1u;
+        const int hl = P16 ? ((P.nb2 + 1) / 2 + 3) & ~3 : (P.nb2 + 3) & ~3;
+        for (int k = lane; k < hl; k += WAVE)
+#pragma unroll
+          for (int h = 0; h < (P16 ? 2 : 1); ++h) {
+            const uint32_t kb = P16 ? 2u * (uint32_t)k + (uint32_t)h : (uint32_t)k;
+            const uint32_t x1 = (kb * rcp) >> 20;
+            if (kb >= (uint32_t)P.nb2 || x1 + (kb - x1 * np1) > (uint32_t)P.n1) continue;
+            const uint32_t kp = min(kb, triC - kb);
+            const uint32_t v = P16 ? (W[kp >> 1] >> ((kp & 1u) << 4)) & 0xffffu : W[kp];
+            if (v > L1) acc2 += (double)v * lnx_of(lnx, v) - fl;
+          }
+      } else
       for (int k = lane; k < h2w; k += WAVE) {
         const uint32_t v = W[k];
         const uint32_t xa = P16 ? (v & 0xffffu) : v, xb = P16 ? (v >> 16) : 0u;
@@ -3229,7 +3277,7 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
       for (int k = lane; k < h2w / 4; k += WAVE) q[k] = make_uint4(0, 0, 0, 0);
     }
     MARK(24);
-    // 1D spectra: one lane per folded inner bin reads (and clears) its R1 replicas; with <= 32 inner
+    // 1D spectra: one lane per folded inner bin reads (and clears) its R1N lane copies; with <= 32 inner
     // bins per population, lanes 0-31 take population 1 and lanes 32-63 population 2 (acca)
     // (every SNP slot of the rows -- 128 per pair, masked ones included -- is counted in one bin of each
     // spectrum: n1a / n1b = slots - bin 0 - bin n_p)
@@ -3241,7 +3289,7 @@ __device__ __forceinline__ void scan_w_small(double* ldsd, uint32_t wgi, uint32_
     // folded bin k (<= n_p) of a population's spectrum, its replicas read and cleared
     auto take1 = [&](uint32_t* H, int k) -> uint32_t {
       if (SFS2D_ABL & 32) return (uint32_t)k;
-      return take_replicas<R1U>(H + k * R1, S1);
+      return take_replicas<R1U>(H + k * R1U, S1);
     };
     if (half1d) {
       const bool pa = lane < 32;
@@ -3345,6 +3393,14 @@ template <bool P16, bool FUSED, int FST, bool CNT, bool GATE = false, bool LEAN 
 __global__ __launch_bounds__(SBLOCK) __attribute__((amdgpu_waves_per_eu(4))) void k_scan_w(SCAN_W_ARGS) {
   extern __shared__ double ldsd[];
   scan_w_small<P16, FUSED, FST, CNT, GATE, LEAN>(ldsd, blockIdx.x, gridDim.x, SCAN_W_PASS);
+}
+
+// k_scan_w's LEAN variants with the triangle-packed window histogram (scan_w_small's TRI), SBN windows per batched
+// finish and R1N lane copies of the 1D histograms; FMASK: FST 3, else 2.  Same arguments, grid and results.
+template <bool P16, bool FUSED, bool FMASK, int SBN, int R1N>
+__global__ __launch_bounds__(SBLOCK) __attribute__((amdgpu_waves_per_eu(4))) void k_scan_wt(SCAN_W_ARGS) {
+  extern __shared__ double ldsd[];
+  scan_w_small<P16, FUSED, FMASK ? 3 : 2, true, true, true, true, SBN, R1N>(ldsd, blockIdx.x, gridDim.x, SCAN_W_PASS);
 }
 
 // K3 for large grids, one wavefront per window (LDS: the wave's histograms only)

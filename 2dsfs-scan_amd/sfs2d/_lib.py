@@ -56,7 +56,7 @@ EXPORTS = [
     "sfs2d_ctx_get_stream", "sfs2d_plan_set_fst_out", "sfs2d_graph_create", "sfs2d_graph_launch", "sfs2d_graph_destroy",
     "sfs2d_plan_create_sliding", "sfs2d_plan_attach_sliding", "sfs2d_plan_null_run", "sfs2d_plan_null_read",
     "sfs2d_plan_null_run_blocks",
-    "sfs2d_plan_scan_variant", "sfs2d_plan_seg_kind", "sfs2d_plan_slots_once",
+    "sfs2d_plan_scan_variant", "sfs2d_plan_scan_packing", "sfs2d_plan_seg_kind", "sfs2d_plan_slots_once",
     "sfs2d_plan_diversity", "sfs2d_plan_diversity_read",
     "sfs2d_plan_create_regions", "sfs2d_plan_attach_regions",
     "sfs2d_plan_spectra", "sfs2d_plan_spectra_read",
@@ -181,6 +181,7 @@ def lib():
     L.sfs2d_plan_scan_kernel.argtypes = [vp]
     L.sfs2d_plan_scan_kernel.restype = C.c_char_p
     L.sfs2d_plan_scan_variant.argtypes = [vp] + [C.POINTER(C.c_int)] * 6
+    L.sfs2d_plan_scan_packing.argtypes = [vp] + [C.POINTER(C.c_int)] * 3
     L.sfs2d_plan_slots_once.argtypes = [vp]
     L.sfs2d_plan_seg_kind.argtypes = [vp]
     L.sfs2d_plan_seg_kind.restype = C.c_char_p

@@ -536,6 +536,14 @@ class Plan:
         self.eng.check(self.eng.lib.sfs2d_plan_scan_variant(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("p16", "fused", "fst", "cnt", "gate", "tri"), (x.value for x in v)))
 
+    def scan_packing(self) -> dict:
+        """{"tri", "sb", "r1"} of a k_scan_w plan (sfs2d_plan_scan_packing): whether it launches k_scan_wt, the lean
+        variants on a triangle-packed window histogram, its windows per batched finish and the lane copies of its 1D
+        window histograms; -1 each for the large-grid kernels."""
+        v = [C.c_int() for _ in range(3)]
+        self.eng.check(self.eng.lib.sfs2d_plan_scan_packing(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("tri", "sb", "r1"), (x.value for x in v)))
+
     def stats(self) -> int:
         v = C.c_uint32()
         self.eng.check(self.eng.lib.sfs2d_plan_stats(self.h, C.byref(v)))

@@ -576,6 +576,12 @@ int sfs2d_plan_slots_once(const sfs2d_plan* plan);
  * 32-bit 2D bins in LDS (a window may hold >= 65,536 SNPs).  An attached plan records at its own launch inside
  * its base's run.  SFS2D_E_ARG before any run (or when no run launched a scan kernel); NULL outputs are skipped */
 int sfs2d_plan_scan_variant(const sfs2d_plan* plan, int* p16, int* fused, int* fst, int* cnt, int* gate, int* tri);
+/* beside it, for k_scan_w plans (-1 each for the large-grid kernels): tri 1 when the plan launches k_scan_wt, the
+ * lean variants on a triangle-packed window histogram (lean plans with n1 = n2, at least 8 windows per resident
+ * wavefront and a workgroup within 80 KB of LDS; SFS2D_TRI=0 at plan creation keeps the lean variant, SFS2D_TRI=1
+ * drops the windows-per-wavefront condition -- same results), sb the windows per batched finish
+ * and r1 the lane copies of the 1D window histograms.  Known from plan creation.  SFS2D_E_ARG for a null plan */
+int sfs2d_plan_scan_packing(const sfs2d_plan* plan, int* tri, int* sb, int* r1);
 /* cumulative number of windows re-evaluated on the exact path (|T| ~ 0: proportionality test) */
 int sfs2d_plan_stats(sfs2d_plan* plan, uint32_t* exact_windows);
 /* last run's error word (0 = ok, else SFS2D_E_KEY / SFS2D_E_GRID, or SFS2D_E_ARG for summed background
